@@ -10,11 +10,18 @@ points, synthetic inputs (seed 1004) already resident in H
 likelihood) -> cross-Gram -> M-right-hand-side triangular solve -> posterior mean and variance.
 
 Prints ONE JSON line (rank 0).  `value` = algorithmic flops of the step / wall time of the
-step (whole job), `e2e_sec` and `cholesky_tflops` are the two halves of the baseline metric.
-`roofline` is measured live with HIP events around every launch of the dominant kernel (the
-MFMA GEMM that carries the panel updates of the blocked Cholesky); `cpu_baseline` times the
-CPU oracle (NumPy/SciPy restatement, same LAPACK entry points as the reference) on a bounded
-sample of the same workload.
+step (whole job), `ms_per_step` = the timed region / --steps, `e2e_sec` the median step.  A
+plain run does only that: set-up, warm-up, the timed steps and the line.
+
+--full adds everything else: HIP events in the timed steps give the per-phase times,
+`cholesky_tflops` (with `e2e_sec` the two halves of the baseline metric) and `roofline` (around
+every launch of the dominant kernel, the MFMA GEMM that carries the panel updates of the blocked
+Cholesky), rocprofv3 child passes its traffic; `cpu_baseline` times the CPU oracle (NumPy/SciPy
+restatement, same LAPACK entry points as the reference) on a bounded sample of the same
+workload, `api_ms` the public API; logp is checked against the oracle's pin; the collective
+counts of the multi-GPU driver are reported.
+
+--dump-outputs DIR writes the arrays the timed path computed in its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -182,6 +189,25 @@ def step_flops(N, M, S=0):
     return f
 
 
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all .npy files of one run together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 arrays as float32, everything else as float64.  An array larger
+    than its share of the budget is written as a fixed sample of its flattened entries (same seed every run, so two builds
+    compare entry for entry)"""
+    os.makedirs(dirname, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // max(1, len(arrays))     # (4096: room for the .npy headers)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            flat = a.reshape(-1)
+            idx = np.random.Generator(np.random.PCG64(1)).choice(flat.size, share // a.itemsize, replace=False)
+            a = flat[np.sort(idx)]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 _REAL_STDOUT = [None]     # a private duplicate of the process's stdout, taken before anything redirects fd 1
 
 
@@ -282,10 +308,10 @@ def _pass_summary(args, N, M, S, pd, pin):
     fl = step_flops(N, M, S)
     o = {'ms_per_step': sec * 1e3, 'ms_per_step_median': med * 1e3, 'value': fl / med / 1e12, 'value_mean': fl / sec / 1e12,
          'logp': pd['logp']}
-    if pin is not None:
+    if pin is not None and args.full:
         o['logp_rel_err'] = abs(pd['logp'] - pin) / abs(pin)
         o['pin_ok'] = bool(o['logp_rel_err'] <= 1e-8)
-    if pd['comm_all'] is not None:
+    if pd['comm_all'] is not None and args.full:
         o['comm'] = {'per_rank': [{k: _per_step(v, args.steps) for k, v in r.items()} for r in pd['comm_all']]}
     return o
 
@@ -323,7 +349,7 @@ def _pass_line(args, world, N, d, M, S, pd, sched):
                           'kernel': 'gemm_nt_kernel<*>: rank 0, staircase launches of the bulk stream + a 1-in-16 sample of the chain stream\'s',
                           'launches_per_step': g['count'] / args.steps, 'avg_launch_ms': g['ms'] / g['count'],
                           'avg_launch_flops': g['work'] / g['count']}
-    if pin is not None:
+    if pin is not None and args.full:
         ln['logp_ref'] = pin
         ln['logp_rel_err'] = abs(pd['logp'] - pin) / abs(pin)
     return ln
@@ -357,8 +383,23 @@ def main():
                                                                      'from host NumPy inputs ("api_ms"; default: on for the one-GPU run)')
     ap.add_argument('--no-api', dest='api', action='store_false')
     ap.add_argument('--panel', dest='nb', type=int, default=0, help='row-block height of the multi-GPU distribution (0 = 1024)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: HIP events in the timed steps (phases, cholesky_tflops, '
+                         'roofline), the measured traffic, the CPU baseline, api_ms, the oracle pin, collective counts')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='write the arrays the timed path computed in its last step as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps (no HIP events in them), the outputs, the line -- nothing else
+        # unless it is asked for by name
+        args.no_prof = True
+        if args.cpu_n < 0:
+            args.cpu_n = 0
+        if args.measure_traffic is None:
+            args.measure_traffic = False
     if args.api is None:
         args.api = args.gpus == 1 and not args.no_prof
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -589,6 +630,24 @@ def main():
             else:
                 result['logp'] = dgp.step(spec_n, spec_f, Xd, Xsd, dd)
 
+    def last_outputs():
+        """--dump-outputs: host copies of what a caller of the timed path receives from its last step, taken right after
+        the timed steps: logp and its two terms, the posterior mean, the per-query sum of squares ss of L^-1 K(X, Xs)
+        (variance = k(x*, x*) - ss), one GPU also L^-1 delta; with draws the mapped posterior draws"""
+        if not args.dump_outputs or rank != 0:
+            return None
+        if use_dist:
+            last = dgp.last
+            o = {'logdet': last['logdet'], 'quad': last['quad'], 'mean': last['mean'], 'ss': last['ss']}
+        else:
+            st = result['stats']
+            o = {'logdet': st['logdet'], 'quad': st['quad'], 'mean': mut[0, :M].cpu().numpy(), 'ss': sst[0, :M].cpu().numpy(),
+                 'linv_delta': at[0, :N].cpu().numpy()}
+        o['logp'] = result['logp']
+        if result.get('draws') is not None:
+            o['draws'] = result['draws']
+        return {k: np.atleast_1d(np.array(v)) for k, v in o.items()}
+
     # ---- the timed region.  Several ranks through the native driver: TWO passes in the same processes (VERDICT r4 item 2) --
     # first with the two communicators never in flight together (G3_DIST_SERIAL_COLL=1: the conservative schedule, which
     # cannot stall on the order of concurrent collectives), its line kept; then the driver is destroyed, the overlapped
@@ -681,7 +740,7 @@ def main():
             overlap_wd = None
         passes[sched] = dict(elapsed=elapsed, step_s=step_s, prof=prof, comm_all=comm_all, logp=float(result['logp']),
                              draws=result.get('draws'), cov_tries=result.get('cov_tries', 0), parallelism=parallelism,
-                             wall_s=time.perf_counter() - t_wall0)
+                             wall_s=time.perf_counter() - t_wall0, outputs=last_outputs())
         if sched != schedules[-1]:
             # the serial pass is complete: its line is ready should the overlapped pass never come back; then the driver goes
             # (communicators, streams, buffers) and the next schedule's is created in the same processes
@@ -706,6 +765,8 @@ def main():
     result['logp'] = pd['logp']
     if pd['draws'] is not None:
         result['draws'], result['cov_tries'] = pd['draws'], pd['cov_tries']
+    if pd['outputs'] is not None:
+        dump_outputs(args.dump_outputs, pd['outputs'])
 
     dist_grad = None
     if use_dist and native and args.grad and S == 0:
@@ -746,8 +807,8 @@ def main():
             'value_note': 'value = algorithmic flops / MEDIAN step time (SURVEY.md 8d); ms_per_step = whole timed region / steps '
                           '(the mean), value_mean the figure that goes with it (rounds 1-3 quoted the mean: compare those with '
                           'value_mean / ms_per_step).  Inputs X, y, Xs are resident in HBM when the timed region starts; SURVEY.md '
-                          '8d\'s logp metric starts at their host-to-device copy (1.3 MB here): api_ms is that host-to-host figure '
-                          'through the public API',
+                          '8d\'s logp metric starts at their host-to-device copy (1.3 MB here): api_ms (--full) is that host-to-host '
+                          'figure through the public API',
             'higher_is_better': True, 'scaling': 'strong',
             'vs_baseline': None, 'dtype': 'f32' if args.f32 else 'f64', 'data': 'synthetic',
             'config': {'workload': args.kernel.upper() + '-kernel GaussianProcess, N=%d d=%d, M=%d test points: Gram + blocked '
@@ -766,6 +827,7 @@ def main():
             if driver_fallback:
                 # a downgrade is never silent: it is in the line, and the run fails unless it was allowed explicitly
                 out['driver_fallback'] = driver_fallback
+        if comm_all is not None and args.full:
             out['comm'] = {'per_rank': [{k: per(v) for k, v in r.items()} for r in comm_all],
                            'driver': 'native' if native else 'python', 'collectives_forced_at_world_1': bool(solo_pg or (native and world == 1)),
                            'transport': ('rccl (library-owned communicators)' if native_transport == 'rccl' else 'host callbacks over gloo (rehearsal)') if native else backend,
@@ -787,8 +849,8 @@ def main():
             out['config']['draws'] = S
             out['draws'] = {'shape': list(dr.shape), 'finite': bool(np.all(np.isfinite(dr))), 'mean': float(np.mean(dr)),
                             'std': float(np.std(dr)), 'cov_jitter_tries': int(result.get('cov_tries', 0))}
-        ph = {k: v['ms'] / args.steps for k, v in prof.items() if v['count']}
-        out['phases_ms'] = ph
+        if args.full:
+            out['phases_ms'] = {k: v['ms'] / args.steps for k, v in prof.items() if v['count']}
         if prof['gram']['count'] and prof['gram']['ms'] > 0:
             # algorithmic bytes of the lower-triangle Gram (N d s read + N(N+1)/2 s written) per second
             out['gram_gbps'] = prof['gram']['work'] / (prof['gram']['ms'] * 1e-3) / 1e9
@@ -863,12 +925,12 @@ def main():
                 out['cpu_baseline']['logp'] = float(lp_cpu)
         # full-size pin: the CPU oracle's logp at this exact configuration (tests/golden/fullsize.json,
         # written once by oracle/gen_fullsize.py in the build container; data, not code)
-        ref = _golden_logp(N, d, M, seed, args.kernel) if not (args.f32 or S > 0) else None
+        ref = _golden_logp(N, d, M, seed, args.kernel) if (args.full and not (args.f32 or S > 0)) else None
         tol = 1e-8
         if ref is not None:
             out['logp_ref'] = ref
             out['logp_rel_err'] = abs(out['logp'] - ref) / abs(ref)
-        elif S > 0:
+        elif S > 0 and args.full:
             # config 5 (warped GP + draws): the fp64 oracle's full-size pin, compared at the fp32 tolerance
             g5 = _golden_c5(N, d, M, seed, S)
             if g5 is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of library variants (G3_LIB_PATH): usage r3_ab.sh <out> <variant .so name or "-" for the product> ...
 OUT=gpurun_out/${1:-r3ab}; shift; mkdir -p $OUT
-B="python bench.py --no-measure-traffic --cpu-n 0 --no-api --skip-events"
+B="python bench.py --full --no-measure-traffic --cpu-n 0 --no-api --skip-events"
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" == "-" ]; then unset G3_LIB_PATH; else export G3_LIB_PATH=$PWD/g3py_amd/lib/$v; fi

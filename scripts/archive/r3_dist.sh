@@ -2,7 +2,7 @@
 # round-3 distributed checks on ONE GPU: the native driver through RCCL with one rank, the python driver through
 # ProcessGroupNCCL with one rank, two-rank rehearsals over gloo of both drivers
 OUT=gpurun_out/${1:-r3d}; mkdir -p $OUT
-B="python bench.py --no-measure-traffic --cpu-n 0 --no-api"
+B="python bench.py --full --no-measure-traffic --cpu-n 0 --no-api"
 echo "== single GPU in-library" | tee -a $OUT/dist.log
 timeout -k 10 300 $B --steps 4 --warmup 1 2>>$OUT/dist.err | tee $OUT/bench_1gpu.json | cut -c1-400 | tee -a $OUT/dist.log
 echo "== native driver, one rank, RCCL" | tee -a $OUT/dist.log

@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=gpurun_out/${1:-r3f}; mkdir -p $OUT
-B="python bench.py --no-measure-traffic --cpu-n 0 --no-api"
+B="python bench.py --full --no-measure-traffic --cpu-n 0 --no-api"
 for nb in 1024 512; do
 echo "== native driver, one rank, RCCL nb=$nb" | tee -a $OUT/dist.log
 G3_FORCE_DIST=1 timeout -k 10 300 $B --steps 4 --warmup 1 --panel $nb 2>>$OUT/dist.err | tee $OUT/bench_dist1_native_rccl_$nb.json | python -c "

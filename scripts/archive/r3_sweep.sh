@@ -5,7 +5,7 @@
 set -o pipefail
 OUT=gpurun_out/${1:-r3a}
 mkdir -p $OUT
-B="python bench.py --no-measure-traffic --cpu-n 0 --no-api"
+B="python bench.py --full --no-measure-traffic --cpu-n 0 --no-api"
 run() { # name, env..., -- args
   name=$1; shift
   envs=()

@@ -1,7 +1,7 @@
 #!/bin/bash
 set -o pipefail
 OUT=gpurun_out/${1:-r3tune}; mkdir -p $OUT
-B="python bench.py --no-measure-traffic --cpu-n 0 --no-api"
+B="python bench.py --full --no-measure-traffic --cpu-n 0 --no-api"
 run() { name=$1; shift; envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   env "${envs[@]}" timeout -k 10 300 $B "$@" 2>>$OUT/sweep.err | python -c "
 import sys, json

@@ -1,6 +1,6 @@
 #!/bin/bash
 cd "$(dirname "$0")/.."
-B="python bench.py --cpu-n 0 --no-api --no-measure-traffic --points 8192 --steps 20 --warmup 3 --skip-events"
+B="python bench.py --full --cpu-n 0 --no-api --no-measure-traffic --points 8192 --steps 20 --warmup 3 --skip-events"
 ms() { python -c "import sys,json; l=[x for x in sys.stdin if x.startswith('{')]; d=json.loads(l[-1]); print('%.3f ms' % d['ms_per_step'])"; }
 export G3_CHAIN_ALLMASK=1
 for hp in 1 0; do

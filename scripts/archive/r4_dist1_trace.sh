@@ -2,7 +2,7 @@
 # kernel-class totals of one evaluation: in-library sweep vs the native multi-GPU driver at one rank
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/dist1; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --cpu-n 0 --no-api --no-measure-traffic --skip-events --steps 3 --warmup 1"
+B="$R/bench.py --full --cpu-n 0 --no-api --no-measure-traffic --skip-events --steps 3 --warmup 1"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/one -- python3 $B > $OUT/one.log 2>&1; echo "one rc=$?"
 export G3_FORCE_DIST=1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/dist -- python3 $B > $OUT/dist.log 2>&1; echo "dist rc=$?"

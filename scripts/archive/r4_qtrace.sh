@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r4q; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for mode in 0 1; do
-G3_CHAIN=$mode G3_CHAIN_WGS=32 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/m$mode -- python3 $R/bench.py --cpu-n 0 --no-api --no-measure-traffic --skip-events --points 8192 --steps 3 --warmup 1 > $OUT/m$mode.log 2>&1; echo "trace $mode rc=$?"
+G3_CHAIN=$mode G3_CHAIN_WGS=32 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/m$mode -- python3 $R/bench.py --full --cpu-n 0 --no-api --no-measure-traffic --skip-events --points 8192 --steps 3 --warmup 1 > $OUT/m$mode.log 2>&1; echo "trace $mode rc=$?"
 done
 cd $R
 for mode in 0 1; do

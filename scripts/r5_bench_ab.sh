@@ -1,7 +1,7 @@
 #!/bin/bash
 # one-GPU configurations with and without the stream-placement probe, same box: scripts/r5_bench_ab.sh <outdir>
 OUT=${1:-gpurun_out/r5_ab}; mkdir -p $OUT
-B="python bench.py --cpu-n 0 --no-measure-traffic --no-api"
+B="python bench.py --full --cpu-n 0 --no-measure-traffic --no-api"
 ms() { python -c "import json,sys; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%.3f ms median, %.3f mean, frac %.3f' % (j['ms_per_step_median'], j['ms_per_step'], j['roofline']['frac']))"; }
 for rep in 1 2; do
 for pr in 2 0; do

@@ -3,7 +3,7 @@
 # compute-side replays P = 2 / 4 / 8 (config 4) and P = 8 (config 5 shape), chain tables.  usage: scripts/r5_evidence.sh [part ...]
 R=${GRAFT_REPO_ROOT:-$PWD}; OUT=$R/gpurun_out/r05e; mkdir -p $OUT $R/gpurun_out/replay
 parts=${@:-bench replay chains}
-B="python bench.py --cpu-n 0 --no-measure-traffic"
+B="python bench.py --full --cpu-n 0 --no-measure-traffic"
 for p in $parts; do
 case $p in
 bench)

@@ -85,10 +85,64 @@ def test_step_flops_and_synthetic_inputs_are_what_survey_8d_states():
     assert bench.usable_cores() >= 1
 
 
+def test_dump_outputs_keeps_float_types_and_samples_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays float32, everything else is written as float64; an array over its share of the budget
+    becomes a fixed sample of its entries -- the same one on every run"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 1 << 16)
+    big = np.arange(1 << 14, dtype=np.float64).reshape(128, 128)
+    arrays = {'logp': np.array([-1.5]), 'mean': np.linspace(0, 1, 7, dtype=np.float32), 'count': np.arange(5), 'big': big}
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    total = 0
+    for name in arrays:
+        a, b = np.load(str(tmp_path / 'a' / (name + '.npy'))), np.load(str(tmp_path / 'b' / (name + '.npy')))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += os.path.getsize(str(tmp_path / 'a' / (name + '.npy')))
+    assert np.load(str(tmp_path / 'a' / 'mean.npy')).dtype == np.float32
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'count.npy')), np.arange(5.0))
+    s = np.load(str(tmp_path / 'a' / 'big.npy'))
+    assert 0 < s.size < big.size and np.all(np.diff(s) > 0) and np.all(np.isin(s, big))   # sorted distinct entries of big
+    assert total <= bench.DUMP_BUDGET_BYTES
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """a plain run carries the headline and nothing measured beside it; --dump-outputs holds the last timed step's
+    results, which agree with the CPU oracle on the same synthetic inputs"""
+    N, M = 4096, 256
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--points', str(N), '--queries', str(M), '--steps', '3',
+                          '--warmup', '1', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith('{'), lines[:5]
+    j = json.loads(lines[0])
+    for k, t in REQUIRED.items():
+        assert k in j and isinstance(j[k], t), (k, type(j.get(k)))
+    assert j['steps'] == 3 and j['warmup'] == 1 and j['dtype'] == 'f64' and j['ms_per_step'] > 0
+    sys.path.insert(0, ROOT)
+    import bench
+    assert abs(j['value'] - bench.step_flops(N, M) / (j['ms_per_step_median'] * 1e-3) / 1e12) <= 1e-9 * j['value']
+    for k in ('roofline', 'cpu_baseline', 'api_ms', 'logp_ref', 'phases_ms', 'cholesky_tflops', 'comm'):
+        assert k not in j, k
+    got = {n: np.load(str(tmp_path / (n + '.npy'))) for n in ('logp', 'logdet', 'quad', 'mean', 'ss', 'linv_delta')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got['mean'].shape == (M,) and got['ss'].shape == (M,) and got['linv_delta'].shape == (N,)
+    assert got['logp'][0] == j['logp']
+    from oracle import g3_oracle as orc
+    X, y, Xs = bench.synth(N, 4, M, 1004)
+    lp, mean, var, _ = orc.cpu_hot_path(X, y, Xs)
+    assert abs(got['logp'][0] - lp) <= 1e-9 * abs(lp)
+    np.testing.assert_allclose(got['mean'], mean, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(np.maximum(1.0 - got['ss'], 0.0), var, rtol=0, atol=1e-8)
+    assert abs(got['quad'][0] - got['linv_delta'].dot(got['linv_delta'])) <= 1e-10 * got['quad'][0]
+
+
 @pytest.mark.gpu
 def test_fresh_small_run_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--points', '4096', '--queries', '256', '--steps', '2',
-                          '--warmup', '1', '--cpu-n', '1024', '--no-measure-traffic', '--no-api'], capture_output=True, text=True,
+                          '--warmup', '1', '--full', '--cpu-n', '1024', '--no-measure-traffic', '--no-api'], capture_output=True, text=True,
                          timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -104,7 +158,7 @@ def test_one_rank_through_rccl_keeps_stdout_to_the_one_line():
     unless bench.py redirects it -- the line must still be alone, and carry the comm block"""
     env = dict(os.environ, G3_FORCE_DIST='1')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--points', '4096', '--queries', '256', '--steps', '1',
-                          '--warmup', '1', '--cpu-n', '0', '--no-measure-traffic', '--no-api'], capture_output=True, text=True,
+                          '--warmup', '1', '--full', '--cpu-n', '0', '--no-measure-traffic', '--no-api'], capture_output=True, text=True,
                          timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -119,7 +173,7 @@ def test_driver_downgrade_is_loud():
     """VERDICT r3 item 3d / ADVICE r3: when the native multi-GPU driver cannot be created the run says so in the line
     (`driver_fallback`) and FAILS, unless G3_DIST_ALLOW_FALLBACK=1 accepts the torch.distributed driver"""
     args = [sys.executable, os.path.join(ROOT, 'bench.py'), '--points', '2048', '--queries', '128', '--steps', '1', '--warmup', '1',
-            '--cpu-n', '0', '--no-measure-traffic', '--no-api']
+            '--full', '--cpu-n', '0', '--no-measure-traffic', '--no-api']
     env = dict(os.environ, G3_FORCE_DIST='1', G3_RCCL_PATH='/nonexistent/librccl.so')
     out = subprocess.run(args, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith('{')]
@@ -138,7 +192,7 @@ def test_two_rank_rehearsal_runs_the_serial_pass_first_and_prints_both_in_one_li
     reproduced the pin.  Rehearsed with two ranks sharing the GPU over gloo (asynchronous callback transport)."""
     env = dict(os.environ, G3_DIST_BACKEND='gloo')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--points', '8192', '--queries', '1024', '--steps', '2',
-                          '--warmup', '1', '--cpu-n', '0', '--no-measure-traffic', '--no-api', '--panel', '512'], capture_output=True,
+                          '--warmup', '1', '--full', '--cpu-n', '0', '--no-measure-traffic', '--no-api', '--panel', '512'], capture_output=True,
                          text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith('{')]
@@ -160,7 +214,7 @@ def test_overlapped_pass_that_never_returns_leaves_the_serial_line_and_a_failure
     exits non-zero.  Forced here with a limit shorter than any pass."""
     env = dict(os.environ, G3_DIST_BACKEND='gloo', G3_BENCH_OVERLAP_LIMIT_S='0.001')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--points', '8192', '--queries', '1024', '--steps', '2',
-                          '--warmup', '1', '--cpu-n', '0', '--no-measure-traffic', '--no-api', '--panel', '512'], capture_output=True,
+                          '--warmup', '1', '--full', '--cpu-n', '0', '--no-measure-traffic', '--no-api', '--panel', '512'], capture_output=True,
                          text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode != 0
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith('{')]

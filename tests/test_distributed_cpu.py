@@ -3,6 +3,7 @@ diagonal-factor broadcast with look-ahead, the panel all-gather and its re-order
 block order, the right-hand-side chunks, the closing all-reduce.  The tile arithmetic is a NumPy test double
 (tests/dist_helpers.py); the expected values come from the oracle."""
 import os
+import random
 import socket
 import sys
 
@@ -14,11 +15,25 @@ from dist_helpers import worker, synth  # noqa: E402
 
 
 def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+    """a free port for rank 0's store, taken from below the kernel's ephemeral range: the ranks bind it seconds later, and
+    on a busy host a port from that range can meanwhile be handed to an outgoing connection (EADDRINUSE)"""
+    lo = 32768
+    try:
+        lo = int(open('/proc/sys/net/ipv4/ip_local_port_range').read().split()[0])
+    except (OSError, ValueError, IndexError):
+        pass
+    rng = random.SystemRandom()
+    for _ in range(100):
+        p = rng.randrange(max(1024, lo - 8192), lo)
+        with socket.socket() as s:
+            try:
+                s.bind(('127.0.0.1', p))
+            except OSError:
+                continue
+        return p
+    with socket.socket() as s:
+        s.bind(('127.0.0.1', 0))
+        return s.getsockname()[1]
 
 
 @pytest.mark.parametrize('world,N,nb,M', [(2, 700, 256, 20), (3, 520, 128, 300), (2, 300, 512, 20), (4, 1100, 128, 130),
