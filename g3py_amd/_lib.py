@@ -18,7 +18,8 @@ G3_GRAM_LOWER, G3_GRAM_SCRUB, G3_GRAM_PAD_EYE = 1, 2, 4
 G3_PAD = 128       # matrices are padded to a multiple of the panel block (G3_LB in the library)
 G3_RHS_PAD = 128   # right-hand-side blocks are padded to a multiple of the 128-row tile
 G3_MAX_BATCH = 4096
-KINDS = dict(SE=0, OU=1, MAT32=2, MAT52=3, RQ=4, COS=5, SIN=6, SINC=7, SM=8, NOISE=9, WN=10)
+KINDS = dict(SE=0, OU=1, MAT32=2, MAT52=3, RQ=4, COS=5, SIN=6, SINC=7, SM=8, NOISE=9, WN=10, DOT=11, NN=12, BW=13, VAR=14)
+G3_DOT_MAXP = 8    # largest exponent of a DOT leaf (the exponent is structure, held in freq[0])
 
 
 class Leaf(C.Structure):

@@ -5,7 +5,7 @@
 #include <stdlib.h>
 
 // ----------------------------------------------------------------------------- context
-extern "C" int g3_version(void) { return 100; }
+extern "C" int g3_version(void) { return 101; }
 
 static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out);
 extern "C" int g3_ctx_create(int device, g3_ctx** out) { return ctx_create_impl(device, nullptr, out); }
@@ -938,21 +938,6 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
 // many hyper-parameter vectors on the same inputs.  All `batch` covariances are built by one
 // Gram launch (grid.z) and factored by ONE sweep whose GEMM / diagonal-block launches carry the
 // batch in grid.y, so a problem too small to fill 256 CUs on its own still does.
-static int same_structure(const g3_kernel_prog* a, const g3_kernel_prog* b) {
-  if (a->nleaf != b->nleaf || a->nprod != b->nprod) return 0;
-  for (int l = 0; l < a->nleaf; ++l) {
-    if (a->leaf[l].kind != b->leaf[l].kind || a->leaf[l].ndims != b->leaf[l].ndims) return 0;
-    for (int k = 0; k < a->leaf[l].ndims; ++k)
-      if (a->leaf[l].dims[k] != b->leaf[l].dims[k]) return 0;
-  }
-  for (int q = 0; q < a->nprod; ++q) {
-    if (a->prod[q].nfac != b->prod[q].nfac) return 0;
-    for (int f = 0; f < a->prod[q].nfac; ++f)
-      if (a->prod[q].fac[f] != b->prod[q].fac[f]) return 0;
-  }
-  return 1;
-}
-
 static int ensure_bbuf(g3_ctx* ctx, size_t bytes) {
   if (ctx->bbuf_bytes >= bytes) return G3_OK;
   if (ctx->bbuf) (void)hipFree(ctx->bbuf);
@@ -1013,7 +998,7 @@ static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch,
   if (mp.progs) {
     for (int b = 0; b < batch; ++b) {
       if (g3i_validate_prog(&mp.progs[b], d)) return -2;
-      if (!same_structure(&mp.progs[0], &mp.progs[b])) return -2;
+      if (!g3h_same_structure(&mp.progs[0], &mp.progs[b])) return -2;
     }
   } else {
     if (g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(&first, d)) return -2;
@@ -1175,7 +1160,7 @@ extern "C" int g3_gp_factor_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tm
   if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
   if (nfield && (!fields || !offsets)) return -4;
   for (int i = 0; i < nfield; ++i)
-    if (!g3h_field_offset_ok(offsets[i])) return -5;
+    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
   MemberProgs mp;
   mp.tmpl = tmpl;
   mp.fields = fields;

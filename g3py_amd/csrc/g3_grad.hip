@@ -188,6 +188,7 @@ extern "C" int g3_grad_layout(const g3_kernel_prog* prog, g3_grad_map* map) {
       case G3_K_SE: case G3_K_OU: case G3_K_MAT32: case G3_K_MAT52:
         map->rate[l] = s; s += nd; break;
       case G3_K_RQ:
+      case G3_K_DOT: case G3_K_NN:      // alpha slot = the bias; the exponent of G3_K_DOT is structure (no slot)
         map->alpha[l] = s++; map->rate[l] = s; s += nd; break;
       case G3_K_COS: case G3_K_SINC:
         map->freq[l] = s; s += nd; break;
@@ -198,6 +199,13 @@ extern "C" int g3_grad_layout(const g3_kernel_prog* prog, g3_grad_map* map) {
   }
   map->nslots = s;
   return G3_OK;
+}
+
+// ARD_DotBias of one pair (metrics.py:130-131; the bias lives in `alpha`)
+__device__ __forceinline__ double dot_metric_d(const g3_leaf& lf, const double* xi, const double* xj) {
+  double m = lf.alpha;
+  for (int k = 0; k < lf.ndims; ++k) m += (xi[lf.dims[k]] * xj[lf.dims[k]]) * (lf.rate[k] * lf.rate[k]);
+  return m;
 }
 
 // thread-private accumulators in LDS: slot-major so that a wave touches 64 consecutive doubles
@@ -323,6 +331,40 @@ __device__ __forceinline__ void leaf_grad(const g3_leaf& lf, int l, const g3_gra
       }
       return;
     }
+    case G3_K_DOT: {   // K = var m^p, m = bias + sum_k rate_k^2 x_ik x_jk: dK/dbias = var p m^(p-1), dK/drate_k = that * 2 rate_k x_ik x_jk
+      const double m = dot_metric_d(lf, xi, xj);
+      const int p = (int)lf.freq[0];
+      double mp1 = 1.0;
+      for (int q = 1; q < p; ++q) mp1 *= m;
+      add(map.var[l], w * (mp1 * m));
+      const double c = wv * (double)p * mp1;
+      add(map.alpha[l], c);
+      for (int k = 0; k < nd; ++k) add(map.rate[l] + k, c * 2.0 * lf.rate[k] * (xi[lf.dims[k]] * xj[lf.dims[k]]));
+      return;
+    }
+    case G3_K_NN: {    // K = var asin(s), s = 2 m12 / (a b), a = 1 + 2 m11, b = 1 + 2 m22:
+      // dK/dtheta = var / sqrt(1 - s^2) * [2 dm12 / (a b) - s (2 dm11 / a + 2 dm22 / b)]
+      const double m12 = dot_metric_d(lf, xi, xj);
+      const double a = 1.0 + 2.0 * dot_metric_d(lf, xi, xi), b = 1.0 + 2.0 * dot_metric_d(lf, xj, xj);
+      const double s = 2.0 * m12 / (a * b);
+      add(map.var[l], w * asin(s));
+      const double c = wv / sqrt(1.0 - s * s);
+      add(map.alpha[l], c * (2.0 / (a * b) - s * (2.0 / a + 2.0 / b)));
+      for (int k = 0; k < nd; ++k) {
+        const double x1 = xi[lf.dims[k]], x2 = xj[lf.dims[k]], r2 = 2.0 * lf.rate[k];
+        add(map.rate[l] + k, c * (2.0 * r2 * x1 * x2 / (a * b) - s * (2.0 * r2 * x1 * x1 / a + 2.0 * r2 * x2 * x2 / b)));
+      }
+      return;
+    }
+    case G3_K_BW: {
+      double p = 1.0;
+      for (int k = 0; k < nd; ++k) p *= fmin(xi[lf.dims[k]], xj[lf.dims[k]]);
+      add(map.var[l], w * p);
+      return;
+    }
+    case G3_K_VAR:
+      add(map.var[l], w);
+      return;
     default:
       return;
   }
@@ -371,6 +413,24 @@ __device__ __forceinline__ double leaf_value(const g3_leaf& lf, const double* xi
       }
       return lf.var * (lf.kind == G3_K_SM ? exp(-2.0 * GG_PI * GG_PI * s) * p : p);
     }
+    case G3_K_DOT: {
+      const double m = dot_metric_d(lf, xi, xj);
+      const int p = (int)lf.freq[0];
+      double v = m;
+      for (int q = 1; q < p; ++q) v *= m;
+      return lf.var * v;
+    }
+    case G3_K_NN: {
+      const double a = 1.0 + 2.0 * dot_metric_d(lf, xi, xi), b = 1.0 + 2.0 * dot_metric_d(lf, xj, xj);
+      return lf.var * asin(2.0 * dot_metric_d(lf, xi, xj) / (a * b));
+    }
+    case G3_K_BW: {
+      double p = 1.0;
+      for (int k = 0; k < nd; ++k) p *= fmin(xi[lf.dims[k]], xj[lf.dims[k]]);
+      return lf.var * p;
+    }
+    case G3_K_VAR:
+      return lf.var;
     default:
       return 0.0;
   }
@@ -876,21 +936,6 @@ static int gram_grad_se(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, con
   return G3_OK;
 }
 
-static bool same_shape(const g3_kernel_prog* a, const g3_kernel_prog* b) {
-  if (a->nleaf != b->nleaf || a->nprod != b->nprod) return false;
-  for (int l = 0; l < a->nleaf; ++l) {
-    if (a->leaf[l].kind != b->leaf[l].kind || a->leaf[l].ndims != b->leaf[l].ndims) return false;
-    for (int k = 0; k < a->leaf[l].ndims; ++k)
-      if (a->leaf[l].dims[k] != b->leaf[l].dims[k]) return false;
-  }
-  for (int q = 0; q < a->nprod; ++q) {
-    if (a->prod[q].nfac != b->prod[q].nfac) return false;
-    for (int f = 0; f < a->prod[q].nfac; ++f)
-      if (a->prod[q].fac[f] != b->prod[q].fac[f]) return false;
-  }
-  return true;
-}
-
 // The gradient kernel generated for the members' common structure (g3_gram_jit.hip::g3_grad_jit): compiled at first use,
 // cached; it accumulates g3_grad_layout's standard slots, routed to the caller's map here.  *handled = false: none
 // (no hipRTC, too many slots, members of different structure) -- the caller interprets.
@@ -902,7 +947,7 @@ static int gram_grad_generated(g3_ctx* ctx, const g3_kernel_prog* progs, int bat
   hipFunction_t fn = g3i_grad_jit_function(ctx, &progs[0], d, dt, &ns);
   if (!fn) return G3_OK;
   for (int b = 1; b < batch; ++b)
-    if (!same_shape(&progs[0], &progs[b])) return G3_OK;
+    if (!g3h_same_structure(&progs[0], &progs[b])) return G3_OK;      // (g3_host.h; incl. the exponent of a dot leaf)
   const int64_t bi0 = row0 / GG_T, bi1 = (row1 + GG_T - 1) / GG_T;
   const int64_t ntiles = bi1 * (bi1 + 1) / 2 - bi0 * (bi0 + 1) / 2;
   int nblocks = (int)(ntiles < 4096 ? ntiles : 4096);
@@ -1232,7 +1277,7 @@ extern "C" int g3_gp_dlogp_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmp
   if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
   if (nfield && (!fields || !offsets)) return -4;
   for (int i = 0; i < nfield; ++i)
-    if (!g3h_field_offset_ok(offsets[i])) return -5;      // the same rule as g3_gp_factor_batched_fields (g3_host.h)
+    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;      // the same rule as g3_gp_factor_batched_fields (g3_host.h)
   std::vector<g3_kernel_prog> progs((size_t)batch, *tmpl);
   for (int b = 0; b < batch; ++b)
     for (int i = 0; i < nfield; ++i)

@@ -28,7 +28,8 @@ typedef long long i64;
 #define GT 64
 #define GTN 128
 #define G3_PI 3.14159265358979323846
-enum { K_SE = 0, K_OU = 1, K_MAT32 = 2, K_MAT52 = 3, K_RQ = 4, K_COS = 5, K_SIN = 6, K_SINC = 7, K_SM = 8, K_NOISE = 9, K_WN = 10 };
+enum { K_SE = 0, K_OU = 1, K_MAT32 = 2, K_MAT52 = 3, K_RQ = 4, K_COS = 5, K_SIN = 6, K_SINC = 7, K_SM = 8, K_NOISE = 9, K_WN = 10,
+       K_DOT = 11, K_NN = 12, K_BW = 13, K_VAR = 14 };
 struct jleaf { int kind; int ndims; int dims[JMAXD]; double var; double alpha; double rate[JMAXD]; double freq[JMAXD]; };
 struct jprod { double coef; int nfac; int fac[JMAXFAC]; int pad[3]; };
 struct jprog { int nleaf; int nprod; double shift; jleaf leaf[JMAXLEAF]; jprod prod[JMAXPROD]; };
@@ -42,7 +43,20 @@ __device__ __forceinline__ T scrub(T v) {        // tt_to_num: NaN -> 0, +-Inf -
   return v;
 }
 
-// one leaf, structure compile-time (L), hyper-parameters from the program; ti / tj: the [cos, sin] rows of the two points
+// ARD_DotBias of one pair over the compile-time columns of leaf L (metrics.py:130-131; the bias lives in `alpha`)
+template <int L, typename XA, typename XB>
+__device__ __forceinline__ T dot_metric(const jleaf& lf, const XA& xa, const XB& xb) {
+  T m = (T)lf.alpha;
+#pragma unroll
+  for (int k = 0; k < jnd[L]; ++k) {
+    const T r = (T)lf.rate[k];
+    m += (xa[jdims[L][k]] * xb[jdims[L][k]]) * (r * r);
+  }
+  return m;
+}
+
+// one leaf, structure compile-time (L), hyper-parameters from the program; ti / tj: the table rows of the two points
+// ([cos, sin] pairs of the periodic leaves, then 1 + 2 m(x, x) of the NN leaves)
 template <int L>
 __device__ __forceinline__ T leaf_eval(const jleaf& lf, const T* xi, const T* xj, bool diag_sym, bool sym, const T* ti, const T* tj) {
   constexpr int kind = jkind[L], nd = jnd[L], to = jtoff[L];
@@ -104,6 +118,22 @@ __device__ __forceinline__ T leaf_eval(const jleaf& lf, const T* xi, const T* xj
       p *= ti[2 * (to + k)] * tj[2 * (to + k)] + ti[2 * (to + k) + 1] * tj[2 * (to + k) + 1];
     }
     return var * (exp(T(-2 * G3_PI * G3_PI) * s) * p);
+  } else if constexpr (kind == K_DOT) {     // var * m^p, p compile-time, by repeated multiplication (the base may be negative)
+    const T m = dot_metric<L>(lf, xi, xj);
+    T v = m;
+#pragma unroll
+    for (int q = 1; q < jpow[L]; ++q) v *= m;
+    return var * v;
+  } else if constexpr (kind == K_NN) {      // kernels.py:348-349 pointwise; a = 1 + 2 m(x, x) prepared once per point of the tile
+    const T a = ti[2 * JNTRIG + jsoff[L]], b = tj[2 * JNTRIG + jsoff[L]];
+    return var * asin(T(2) * dot_metric<L>(lf, xi, xj) / (a * b));
+  } else if constexpr (kind == K_BW) {      // metrics.py:54-56
+    T p = T(1);
+#pragma unroll
+    for (int k = 0; k < nd; ++k) p *= fmin(xi[jdims[L][k]], xj[jdims[L][k]]);
+    return var * p;
+  } else if constexpr (kind == K_VAR) {
+    return var;
   } else {
     return T(0);
   }
@@ -154,7 +184,7 @@ g3_gram_jit(const jprog* __restrict__ prog, const T* __restrict__ X1, i64 n1, i6
   if (i0 >= n1pad || j0 >= n2pad) return;
   extern __shared__ __attribute__((aligned(16))) char smem_g[];
   constexpr int dp = JD | 1;                // odd row stride: conflict-free column-varying reads
-  constexpr int tstride = 2 * JNTRIG + 1;
+  constexpr int tstride = (2 * JNTRIG + JNSELF) | 1;     // odd: [cos, sin] pairs, then the NN leaves' self terms
   T* xi_s = reinterpret_cast<T*>(smem_g);
   T* xj_s = xi_s + GT * dp;
   T* trig_s = xj_s + GTN * dp;
@@ -177,6 +207,21 @@ g3_gram_jit(const jprog* __restrict__ prog, const T* __restrict__ X1, i64 n1, i6
       const T th = T(2 * G3_PI) * (T)prog->leaf[l].freq[k] * x;
       trig_s[pnt * tstride + 2 * t] = cos(th);
       trig_s[pnt * tstride + 2 * t + 1] = sin(th);
+    }
+  }
+  if constexpr (JNSELF > 0) {
+    if constexpr (JNTRIG == 0) __syncthreads();
+    // 1 + 2 m(x, x) of every NN leaf for the 64 + 128 points of the tile: once per point instead of once per pair
+    for (int e = tid; e < (GT + GTN) * JNSELF; e += 256) {
+      const int pnt = e / JNSELF, sl = e - pnt * JNSELF;
+      const int l = jsleaf[sl];
+      const T* x = pnt < GT ? xi_s + pnt * dp : xj_s + (pnt - GT) * dp;
+      T m = (T)prog->leaf[l].alpha;
+      for (int k = 0; k < jnd[l]; ++k) {
+        const T r = (T)prog->leaf[l].rate[k], xv = x[jdims[l][k]];
+        m += (xv * xv) * (r * r);
+      }
+      trig_s[pnt * tstride + 2 * JNTRIG + sl] = T(1) + T(2) * m;
     }
   }
   __syncthreads();
@@ -262,7 +307,8 @@ typedef long long i64;
 #define GG_T 64
 #define GG_THREADS 256
 #define GG_PI 3.14159265358979323846
-enum { K_SE = 0, K_OU = 1, K_MAT32 = 2, K_MAT52 = 3, K_RQ = 4, K_COS = 5, K_SIN = 6, K_SINC = 7, K_SM = 8, K_NOISE = 9, K_WN = 10 };
+enum { K_SE = 0, K_OU = 1, K_MAT32 = 2, K_MAT52 = 3, K_RQ = 4, K_COS = 5, K_SIN = 6, K_SINC = 7, K_SM = 8, K_NOISE = 9, K_WN = 10,
+       K_DOT = 11, K_NN = 12, K_BW = 13, K_VAR = 14 };
 struct jleaf { int kind; int ndims; int dims[JMAXD]; double var; double alpha; double rate[JMAXD]; double freq[JMAXD]; };
 struct jprod { double coef; int nfac; int fac[JMAXFAC]; int pad[3]; };
 struct jprog { int nleaf; int nprod; double shift; jleaf leaf[JMAXLEAF]; jprod prod[JMAXPROD]; };
@@ -272,7 +318,8 @@ JTABLES
 
 // the standard slot layout of g3_grad_layout: per leaf var, [alpha], [freq...], [rate...]
 constexpr int slots_of(int kind, int nd) {
-  return (kind == K_NOISE || kind == K_WN) ? 1 : kind == K_RQ ? 2 + nd : (kind == K_SIN || kind == K_SM) ? 1 + 2 * nd : 1 + nd;
+  return (kind == K_NOISE || kind == K_WN || kind == K_BW || kind == K_VAR) ? 1
+         : (kind == K_RQ || kind == K_DOT || kind == K_NN) ? 2 + nd : (kind == K_SIN || kind == K_SM) ? 1 + 2 * nd : 1 + nd;
 }
 constexpr int slot_base(int L) {
   int s = 0;
@@ -289,12 +336,42 @@ constexpr bool any_multi() {
 }
 constexpr bool JMULTI = any_multi();
 
-// value of leaf L (variance included) for the pair -- g3_grad.hip::leaf_value with the kind folded
+// ARD_DotBias of one pair over the compile-time columns of leaf L (metrics.py:130-131; the bias lives in `alpha`)
 template <int L>
-__device__ __forceinline__ double leaf_val(const jleaf& lf, const double* xi, const double* xj, bool diag) {
+__device__ __forceinline__ double dot_metric(const jleaf& lf, const double* xa, const double* xb) {
+  double m = lf.alpha;
+#pragma unroll
+  for (int k = 0; k < jnd[L]; ++k) m += (xa[jdims[L][k]] * xb[jdims[L][k]]) * (lf.rate[k] * lf.rate[k]);
+  return m;
+}
+template <int L>
+__device__ __forceinline__ double dot_power(double m) {     // m^(p - 1), p compile-time
+  double v = 1.0;
+#pragma unroll
+  for (int q = 1; q < jpow[L]; ++q) v *= m;
+  return v;
+}
+
+// value of leaf L (variance included) for the pair -- g3_grad.hip::leaf_value with the kind folded; si / sj: m(x, x) of the
+// NN leaves for the two points (prepared once per point of the tile)
+template <int L>
+__device__ __forceinline__ double leaf_val(const jleaf& lf, const double* xi, const double* xj, bool diag, const double* si, const double* sj) {
   constexpr int kind = jkind[L], nd = jnd[L];
   if constexpr (kind == K_NOISE || kind == K_WN) {
     return diag ? lf.var : 0.0;
+  } else if constexpr (kind == K_DOT) {
+    const double m = dot_metric<L>(lf, xi, xj);
+    return lf.var * (dot_power<L>(m) * m);
+  } else if constexpr (kind == K_NN) {
+    const double a = 1.0 + 2.0 * si[jsoff[L]], b = 1.0 + 2.0 * sj[jsoff[L]];
+    return lf.var * asin(2.0 * dot_metric<L>(lf, xi, xj) / (a * b));
+  } else if constexpr (kind == K_BW) {
+    double p = 1.0;
+#pragma unroll
+    for (int k = 0; k < nd; ++k) p *= fmin(xi[jdims[L][k]], xj[jdims[L][k]]);
+    return lf.var * p;
+  } else if constexpr (kind == K_VAR) {
+    return lf.var;
   } else if constexpr (kind == K_SE || kind == K_MAT32 || kind == K_MAT52 || kind == K_RQ) {
     double D = 0.0;
 #pragma unroll
@@ -337,12 +414,39 @@ __device__ __forceinline__ double leaf_val(const jleaf& lf, const double* xi, co
 
 // w * d(var * k)/d(param) for every parameter of leaf L into its slots -- g3_grad.hip::leaf_grad with the kind folded
 template <int L>
-__device__ __forceinline__ void leaf_grad(const jleaf& lf, const double* xi, const double* xj, bool diag, double w, double (&acc)[JNSA]) {
+__device__ __forceinline__ void leaf_grad(const jleaf& lf, const double* xi, const double* xj, bool diag, double w, double (&acc)[JNSA],
+                                          const double* si, const double* sj) {
   constexpr int kind = jkind[L], nd = jnd[L], s0 = slot_base(L);
   const double var = lf.var;
   const double wv = w * var;
   if constexpr (kind == K_NOISE || kind == K_WN) {
     if (diag) acc[s0] += w;
+  } else if constexpr (kind == K_DOT) {   // slots: var, bias, rate[k].  K = var m^p: dK/dbias = var p m^(p-1), dK/drate_k = that * 2 rate_k x_ik x_jk
+    const double m = dot_metric<L>(lf, xi, xj), mp1 = dot_power<L>(m);
+    acc[s0] += w * (mp1 * m);
+    const double c = wv * (double)jpow[L] * mp1;
+    acc[s0 + 1] += c;
+#pragma unroll
+    for (int k = 0; k < nd; ++k) acc[s0 + 2 + k] += c * 2.0 * lf.rate[k] * (xi[jdims[L][k]] * xj[jdims[L][k]]);
+  } else if constexpr (kind == K_NN) {    // K = var asin(s), s = 2 m12 / (a b): dK/dtheta = var / sqrt(1 - s^2) [2 dm12 / (a b) - s (2 dm11 / a + 2 dm22 / b)]
+    const double a = 1.0 + 2.0 * si[jsoff[L]], b = 1.0 + 2.0 * sj[jsoff[L]];
+    const double iab = 1.0 / (a * b), ia = 1.0 / a, ib = 1.0 / b;
+    const double s = 2.0 * dot_metric<L>(lf, xi, xj) * iab;
+    acc[s0] += w * asin(s);
+    const double c = wv / sqrt(1.0 - s * s);
+    acc[s0 + 1] += c * (2.0 * iab - s * (2.0 * ia + 2.0 * ib));
+#pragma unroll
+    for (int k = 0; k < nd; ++k) {
+      const double x1 = xi[jdims[L][k]], x2 = xj[jdims[L][k]], r2 = 2.0 * lf.rate[k];
+      acc[s0 + 2 + k] += c * (2.0 * r2 * x1 * x2 * iab - s * (2.0 * r2 * x1 * x1 * ia + 2.0 * r2 * x2 * x2 * ib));
+    }
+  } else if constexpr (kind == K_BW) {
+    double p = 1.0;
+#pragma unroll
+    for (int k = 0; k < nd; ++k) p *= fmin(xi[jdims[L][k]], xj[jdims[L][k]]);
+    acc[s0] += w * p;
+  } else if constexpr (kind == K_VAR) {
+    acc[s0] += w;
   } else if constexpr (kind == K_SE || kind == K_MAT32 || kind == K_MAT52 || kind == K_RQ) {
     constexpr int srate = s0 + (kind == K_RQ ? 2 : 1);
     double D = 0.0;
@@ -444,10 +548,11 @@ __device__ __forceinline__ void leaf_grad(const jleaf& lf, const double* xi, con
 }
 
 template <int L>
-__device__ __forceinline__ void all_vals(const jprog* __restrict__ prog, const double* xi, const double* xj, bool diag, double (&lv)[JNLA]) {
+__device__ __forceinline__ void all_vals(const jprog* __restrict__ prog, const double* xi, const double* xj, bool diag, double (&lv)[JNLA],
+                                         const double* si, const double* sj) {
   if constexpr (L < JNL) {
-    lv[L] = leaf_val<L>(prog->leaf[L], xi, xj, diag);
-    all_vals<L + 1>(prog, xi, xj, diag, lv);
+    lv[L] = leaf_val<L>(prog->leaf[L], xi, xj, diag, si, sj);
+    all_vals<L + 1>(prog, xi, xj, diag, lv, si, sj);
   }
 }
 
@@ -472,11 +577,11 @@ __device__ __forceinline__ double dk_dleaf(const jprog* __restrict__ prog, const
 
 template <int L>
 __device__ __forceinline__ void all_grads(const jprog* __restrict__ prog, const double* xi, const double* xj, bool diag, double g,
-                                          const double (&lv)[JNLA], double (&acc)[JNSA]) {
+                                          const double (&lv)[JNLA], double (&acc)[JNSA], const double* si, const double* sj) {
   if constexpr (L < JNL) {
     const double q = dk_dleaf<L>(prog, lv);
-    if (q != 0.0) leaf_grad<L>(prog->leaf[L], xi, xj, diag, g * q, acc);
-    all_grads<L + 1>(prog, xi, xj, diag, g, lv, acc);
+    if (q != 0.0) leaf_grad<L>(prog->leaf[L], xi, xj, diag, g * q, acc, si, sj);
+    all_grads<L + 1>(prog, xi, xj, diag, g, lv, acc, si, sj);
   }
 }
 
@@ -491,6 +596,7 @@ g3_grad_jit(const jprog* __restrict__ prog, const T* __restrict__ X, i64 N, i64 
   constexpr int dp = JD | 1;
   __shared__ double xi_s[GG_T * dp], xj_s[GG_T * dp], ai_s[GG_T], aj_s[GG_T];
   __shared__ double red[JNSA * (GG_THREADS / 64)];
+  __shared__ double si_s[JNSELF > 0 ? GG_T * JNSELF : 1], sj_s[JNSELF > 0 ? GG_T * JNSELF : 1];   // m(x, x) of the NN leaves per point
   const int tid = threadIdx.x;
   double acc[JNSA];
 #pragma unroll
@@ -513,6 +619,17 @@ g3_grad_jit(const jprog* __restrict__ prog, const T* __restrict__ X, i64 N, i64 
     if (tid < GG_T) ai_s[tid] = i0 + tid < row1 ? (double)alpha[i0 + tid] : 0.0;
     else if (tid < 2 * GG_T) aj_s[tid - GG_T] = j0 + tid - GG_T < N ? (double)alpha[j0 + tid - GG_T] : 0.0;
     __syncthreads();
+    if constexpr (JNSELF > 0) {
+      for (int e = tid; e < 2 * GG_T * JNSELF; e += GG_THREADS) {
+        const int pnt = e / JNSELF, sl = e - pnt * JNSELF;
+        const int l = jsleaf[sl];
+        const double* x = pnt < GG_T ? xi_s + pnt * dp : xj_s + (pnt - GG_T) * dp;
+        double m = prog->leaf[l].alpha;
+        for (int k = 0; k < jnd[l]; ++k) m += (x[jdims[l][k]] * x[jdims[l][k]]) * (prog->leaf[l].rate[k] * prog->leaf[l].rate[k]);
+        if (pnt < GG_T) si_s[pnt * JNSELF + sl] = m; else sj_s[(pnt - GG_T) * JNSELF + sl] = m;
+      }
+      __syncthreads();
+    }
     const int c = tid & (GG_T - 1);
     const i64 j = j0 + c;
     double xj[JD];
@@ -525,12 +642,15 @@ g3_grad_jit(const jprog* __restrict__ prog, const T* __restrict__ X, i64 N, i64 
       const double* xi = xi_s + rr * dp;
       const double g = (diag ? 0.5 : 1.0) * (ai_s[rr] * aj_s[c] - (double)G[(i - row0) * ldg + j]);
       double lv[JNLA];
-      if constexpr (JMULTI) all_vals<0>(prog, xi, xj, diag, lv);
+      const double* si = nullptr;
+      const double* sj = nullptr;
+      if constexpr (JNSELF > 0) { si = si_s + rr * JNSELF; sj = sj_s + c * JNSELF; }
+      if constexpr (JMULTI) all_vals<0>(prog, xi, xj, diag, lv, si, sj);
       else {
 #pragma unroll
         for (int l = 0; l < JNLA; ++l) lv[l] = 1.0;
       }
-      all_grads<0>(prog, xi, xj, diag, g, lv, acc);
+      all_grads<0>(prog, xi, xj, diag, g, lv, acc, si, sj);
     }
   }
   // block reduction
@@ -592,7 +712,7 @@ Rtc* rtc() {      // (g_mu held)
 
 // the structure of a program: everything the generated kernel is specialised on, as the cache key AND as the header
 // of constexpr tables.  Hyper-parameters (var, rate, freq, alpha, coef, shift) are data and not part of it.
-std::string structure_tables(const g3_kernel_prog* p, int d, int* ntrig_out) {
+std::string structure_tables(const g3_kernel_prog* p, int d, int* ntrig_out, int* nself_out = nullptr) {
   std::string s;
   char b[256];
   auto arr = [&](const char* name, int n, auto get) {
@@ -605,6 +725,18 @@ std::string structure_tables(const g3_kernel_prog* p, int d, int* ntrig_out) {
   s += b;
   arr("jkind", nl, [&](int i) { return (int)p->leaf[i].kind; });
   arr("jnd", nl, [&](int i) { return (int)p->leaf[i].ndims; });
+  // the exponent of a dot-group leaf is structure (include/g3hip.h: G3_K_DOT); 1 for every other kind
+  arr("jpow", nl, [&](int i) { return p->leaf[i].kind == G3_K_DOT ? (int)p->leaf[i].freq[0] : 1; });
+  // NN leaves: index of the leaf's self term 1 + 2 m(x, x) in the per-point table (-1: none)
+  int nself = 0;
+  arr("jsoff", nl, [&](int i) { return p->leaf[i].kind == G3_K_NN ? nself++ : -1; });
+  snprintf(b, sizeof(b), "#define JNSELF %d\n", nself);
+  s += b;
+  {
+    int li = 0;
+    arr("jsleaf", nself, [&](int) { while (p->leaf[li].kind != G3_K_NN) ++li; return li++; });
+  }
+  if (nself_out) *nself_out = nself;
   s += "constexpr int jdims[" + std::to_string(nl > 0 ? nl : 1) + "][JMAXD] = {";
   for (int l = 0; l < (nl > 0 ? nl : 1); ++l) {
     s += l ? ", {" : "{";
@@ -664,8 +796,10 @@ int compile_structure(const std::string& tables, g3_dtype dt, std::string* code,
   snprintf(o4, sizeof(o4), "-DJMAXPROD=%d", G3_MAXPROD);
   snprintf(o5, sizeof(o5), "-DJMAXFAC=%d", G3_MAXFAC);
   snprintf(o6, sizeof(o6), "-DJPROG_BYTES=%d", (int)sizeof(g3_kernel_prog));
-  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", o1, o2, o3, o4, o5, o6, o7};
-  const int cr = r->CompileProgram(pr, 10, opts);
+  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", o1, o2, o3, o4, o5, o6, o7,
+                        "-Rpass-analysis=kernel-resource-usage"};
+  // G3_JIT_REMARKS=1: the compiler's resource report (VGPRs, scratch, LDS, occupancy) in the log g3_*_jit_check returns
+  const int cr = r->CompileProgram(pr, g3h_env_int("G3_JIT_REMARKS", 0) ? 11 : 10, opts);
   size_t ls = 0;
   r->GetProgramLogSize(pr, &ls);
   if (ls > 1) { log->assign(ls, '\0'); r->GetProgramLog(pr, &(*log)[0]); }
@@ -686,7 +820,8 @@ int std_grad_slots(const g3_kernel_prog* p) {
   int s = 0;
   for (int l = 0; l < p->nleaf; ++l) {
     const int kd = p->leaf[l].kind, nd = p->leaf[l].ndims;
-    s += (kd == G3_K_NOISE || kd == G3_K_WN) ? 1 : kd == G3_K_RQ ? 2 + nd : (kd == G3_K_SIN || kd == G3_K_SM) ? 1 + 2 * nd : 1 + nd;
+    s += (kd == G3_K_NOISE || kd == G3_K_WN || kd == G3_K_BW || kd == G3_K_VAR) ? 1
+         : (kd == G3_K_RQ || kd == G3_K_DOT || kd == G3_K_NN) ? 2 + nd : (kd == G3_K_SIN || kd == G3_K_SM) ? 1 + 2 * nd : 1 + nd;
   }
   return s;
 }
@@ -758,8 +893,8 @@ int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_p
                  int64_t ldx1, const void* X2, int64_t n2, int64_t ldx2, int d, g3_dtype dt, void* K, int64_t ldk, int64_t n1pad,
                  int64_t n2pad, unsigned flags, int sym, int64_t kstride, int64_t diag_off, dim3 grid) {
   if (ctx->tune.gram_interpret || !ctx->tune.gram_jit) return 1;
-  int ntrig = 0;
-  const std::string tables = structure_tables(prog_host, d, &ntrig);
+  int ntrig = 0, nself = 0;
+  const std::string tables = structure_tables(prog_host, d, &ntrig, &nself);
   if (ntrig > 24) return 1;
   const std::string key = std::to_string(ctx->device) + (dt == G3_F64 ? "|f64|" : "|f32|") + tables;
   Entry ent;
@@ -788,7 +923,8 @@ int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_p
   }
   if (ent.failed || !ent.fn) return 1;
   const size_t es = g3_esize(dt);
-  const size_t lds = (size_t)(64 + 128) * ((d | 1) + (ntrig ? 2 * ntrig + 1 : 0)) * es;
+  const int ntab = 2 * ntrig + nself;      // per point: [cos, sin] pairs, then the NN leaves' self terms (odd row stride)
+  const size_t lds = (size_t)(64 + 128) * ((d | 1) + (ntab ? (ntab | 1) : 0)) * es;
   if (lds > 96 * 1024) return 1;
   grid.z = (unsigned)(batch > 1 ? batch : 1);
   struct {

@@ -517,8 +517,12 @@ static inline int g3h_validate_prog(const g3_kernel_prog* p, int d) {
   if (p->nleaf < 0 || p->nleaf > G3_MAXLEAF || p->nprod < 0 || p->nprod > G3_MAXPROD) return 1;
   for (int l = 0; l < p->nleaf; ++l) {
     const g3_leaf& lf = p->leaf[l];
-    if (lf.kind < 0 || lf.kind > G3_K_WN) return 1;
+    if (lf.kind < 0 || lf.kind > G3_K_LAST) return 1;
     if (lf.ndims < 0 || lf.ndims > G3_MAXD) return 1;
+    if (lf.kind == G3_K_DOT) {      // the exponent (structure, held in freq[0]): an integer in 1 .. G3_DOT_MAXP
+      const double pw = lf.freq[0];
+      if (!(pw >= 1.0 && pw <= (double)G3_DOT_MAXP) || (double)(int)pw != pw) return 1;
+    }
     for (int k = 0; k < lf.ndims; ++k)
       if (lf.dims[k] < 0 || lf.dims[k] >= d) return 1;
   }
@@ -528,6 +532,25 @@ static inline int g3h_validate_prog(const g3_kernel_prog* p, int d) {
       if (p->prod[q].fac[f] < 0 || p->prod[q].fac[f] >= p->nleaf) return 1;
   }
   return 0;
+}
+
+// Do two programs share ONE structure -- everything a generated kernel is compiled for and a batched launch assumes
+// equal for its members: leaf kinds, columns, the exponent of a dot-group leaf (freq[0] of G3_K_DOT), the product table?
+// Hyper-parameters (var, alpha, rate, freq, coef, shift) are data and may differ.
+static inline bool g3h_same_structure(const g3_kernel_prog* a, const g3_kernel_prog* b) {
+  if (a->nleaf != b->nleaf || a->nprod != b->nprod) return false;
+  for (int l = 0; l < a->nleaf; ++l) {
+    if (a->leaf[l].kind != b->leaf[l].kind || a->leaf[l].ndims != b->leaf[l].ndims) return false;
+    if (a->leaf[l].kind == G3_K_DOT && a->leaf[l].freq[0] != b->leaf[l].freq[0]) return false;
+    for (int k = 0; k < a->leaf[l].ndims; ++k)
+      if (a->leaf[l].dims[k] != b->leaf[l].dims[k]) return false;
+  }
+  for (int q = 0; q < a->nprod; ++q) {
+    if (a->prod[q].nfac != b->prod[q].nfac) return false;
+    for (int f = 0; f < a->prod[q].nfac; ++f)
+      if (a->prod[q].fac[f] != b->prod[q].fac[f]) return false;
+  }
+  return true;
 }
 
 // ---- chains: ONE template program plus the doubles that differ per member (g3_gp_factor_batched_fields,
@@ -541,4 +564,15 @@ static inline int g3h_field_offset_ok(int32_t off) {
     return ((size_t)off - l0) % sizeof(g3_leaf) >= offsetof(g3_leaf, var);
   if ((size_t)off >= p0) return ((size_t)off - p0) % sizeof(g3_prod) == offsetof(g3_prod, coef);
   return 0;
+}
+// ... and, given the template, never the exponent of a dot-group leaf (freq[0] of a G3_K_DOT leaf): it is structure -- the
+// generated kernels are compiled for it -- so no member may overwrite it
+static inline int g3h_field_offset_ok_tmpl(const g3_kernel_prog* tmpl, int32_t off) {
+  if (!g3h_field_offset_ok(off)) return 0;
+  const size_t l0 = offsetof(g3_kernel_prog, leaf);
+  if ((size_t)off >= l0 && (size_t)off < l0 + sizeof(g3_leaf) * G3_MAXLEAF) {
+    const size_t l = ((size_t)off - l0) / sizeof(g3_leaf), in = ((size_t)off - l0) % sizeof(g3_leaf);
+    if (in == offsetof(g3_leaf, freq) && tmpl->leaf[l].kind == G3_K_DOT) return 0;
+  }
+  return 1;
 }

@@ -1,7 +1,7 @@
 // Evaluation of a kernel expression (g3_kernel_prog: shift + sum of products of leaves) for ONE pair of points, as device
-// functions: the interpreter of the Gram kernel (g3_gram.hip) and of the one-workgroup-per-member chain kernel
-// (g3_potrf.hip::small_factor_kernel, which builds its member's covariance itself).  Formulas and their reference lines:
-// g3py/processes/hypers/metrics.py:30-35,89-102; kernels.py:360-487.
+// functions: the interpreter of the Gram kernel and of gram_diag_kernel (g3_gram.hip).  Chains get their members'
+// covariances from the batched Gram launch (member in grid.z, generated or interpreted), not from a kernel of their own.
+// Formulas and their reference lines: g3py/processes/hypers/metrics.py:30-35,54-56,89-102,111-131; kernels.py:82-93,293-487.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +27,18 @@ __host__ __device__ __forceinline__ bool leaf_has_trig(int kind) {
 // branch-free sequence and wins by 2-3 %.  The library routine is used; the hand-written one was removed in round 4 (its A/B numbers stay in profiles/r03_gram.md).
 __device__ __forceinline__ double g3_exp(double x) { return exp(x); }
 __device__ __forceinline__ float g3_exp(float x) { return exp(x); }
+
+// ARD_DotBias of one pair, metrics.py:130-131 (the bias lives in `alpha`; ARD_Dot, metrics.py:112-113, is bias = 0)
+template <typename T>
+__device__ __forceinline__ T dot_metric(const g3_leaf& lf, const T* xi, const T* xj) {
+  T m = (T)lf.alpha;
+  for (int k = 0; k < lf.ndims; ++k) {
+    const int c = lf.dims[k];
+    const T r = (T)lf.rate[k];
+    m += (xi[c] * xj[c]) * (r * r);
+  }
+  return m;
+}
 
 template <typename T>
 __device__ __forceinline__ T leaf_eval(const g3_leaf& lf, const T* xi, const T* xj, bool diag_sym,
@@ -127,6 +139,28 @@ __device__ __forceinline__ T leaf_eval(const g3_leaf& lf, const T* xi, const T* 
       }
       return var * (exp(T(-2 * G3_PI * G3_PI) * s) * p);
     }
+    // ---- dot-product family: functions of x_i, x_j themselves (same formula for the square and the cross case)
+    case G3_K_DOT: {   // var * (bias + sum_k rate_k^2 x_ik x_jk)^p, p >= 1 by repeated multiplication (the base may be negative)
+      const T m = dot_metric<T>(lf, xi, xj);
+      const int p = (int)lf.freq[0];
+      T v = m;
+      for (int q = 1; q < p; ++q) v *= m;
+      return var * v;
+    }
+    case G3_K_NN: {    // kernels.py:348-349, pointwise; the self terms are recomputed per pair here (2 nd FMAs)
+      const T m12 = dot_metric<T>(lf, xi, xj), m11 = dot_metric<T>(lf, xi, xi), m22 = dot_metric<T>(lf, xj, xj);
+      return var * asin(T(2) * m12 / ((T(1) + T(2) * m11) * (T(1) + T(2) * m22)));
+    }
+    case G3_K_BW: {    // metrics.py:54-56
+      T p = T(1);
+      for (int k = 0; k < nd; ++k) {
+        const int c = lf.dims[k];
+        p *= fmin(xi[c], xj[c]);
+      }
+      return var * p;
+    }
+    case G3_K_VAR:
+      return var;
     default:
       return T(0);
   }

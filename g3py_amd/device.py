@@ -449,6 +449,15 @@ def spec_leaves(spec):
     return leaves
 
 
+# leaf kind -> which entry of the leaf's spec tuple feeds the `rate` / `alpha` / `freq` fields of g3_leaf (entry 1 is always
+# `var`).  compile_spec, compile_spec_rows and the slot -> hyper routing of dlogp (processes/gaussian.py) all read it.  DOT =
+# (var, rate, bias, p, dims) and NN = (var, rate, bias, dims) keep their bias in `alpha`; p is structure (freq[0], no gradient slot).
+LEAF_FIELDS = {'SE': dict(rate=2), 'OU': dict(rate=2), 'MAT32': dict(rate=2), 'MAT52': dict(rate=2),
+               'RQ': dict(rate=2, alpha=3), 'COS': dict(freq=2), 'SINC': dict(freq=2),
+               'SIN': dict(freq=2, rate=3), 'SM': dict(freq=2, rate=3), 'NOISE': {}, 'WN': {},
+               'DOT': dict(rate=2, alpha=3), 'NN': dict(rate=2, alpha=3), 'BW': {}, 'VAR': {}}
+
+
 def compile_spec(spec, d):
     """spec tree -> g3_kernel_prog for an input with d columns."""
     leaves = []
@@ -465,7 +474,7 @@ def compile_spec(spec, d):
         kind = lf[0]
         L.kind = _lib.KINDS[kind]
         L.var = float(lf[1])
-        dims = lf[-1] if kind != 'NOISE' else None
+        dims = lf[-1] if kind not in ('NOISE', 'VAR') else None
         dims = np.arange(d) if dims is None else np.atleast_1d(np.asarray(dims)).astype(int)
         dims = np.where(dims < 0, dims + d, dims)
         if len(dims) > _lib.G3_MAXD or (len(dims) and (dims.min() < 0 or dims.max() >= d)):
@@ -478,16 +487,16 @@ def compile_spec(spec, d):
             v = np.broadcast_to(np.asarray(v, dtype=np.float64), (len(dims),))
             for k in range(len(dims)):
                 dst[k] = float(v[k])
-        if kind in ('SE', 'OU', 'MAT32', 'MAT52'):
-            put(L.rate, lf[2])
-        elif kind == 'RQ':
-            put(L.rate, lf[2])
-            L.alpha = float(lf[3])
-        elif kind in ('COS', 'SINC'):
-            put(L.freq, lf[2])
-        elif kind in ('SIN', 'SM'):
-            put(L.freq, lf[2])
-            put(L.rate, lf[3])
+        for member, idx in LEAF_FIELDS[kind].items():
+            if member == 'alpha':
+                L.alpha = float(lf[idx])
+            else:
+                put(getattr(L, member), lf[idx])
+        if kind == 'DOT':
+            p_exp = lf[4]
+            if float(p_exp) != int(p_exp) or not 1 <= int(p_exp) <= _lib.G3_DOT_MAXP:
+                raise G3Error('the exponent of a DOT leaf must be an integer in 1 .. %d (got %r)' % (_lib.G3_DOT_MAXP, p_exp))
+            L.freq[0] = float(int(p_exp))
     for p, (coef, fac) in enumerate(terms):
         if len(fac) > _lib.G3_MAXFAC:
             raise G3Error('product of more than %d kernels is not supported' % _lib.G3_MAXFAC)
@@ -523,15 +532,7 @@ def compile_spec_rows(spec_rows, spec0, d, B):
     for i, lf in enumerate(leaves):
         kind, nd = lf[0], int(tmpl.leaf[i].ndims)
         put(i, 'var', lf[1], 1)
-        if kind in ('SE', 'OU', 'MAT32', 'MAT52'):
-            put(i, 'rate', lf[2], nd)
-        elif kind == 'RQ':
-            put(i, 'rate', lf[2], nd)
-            put(i, 'alpha', lf[3], 1)
-        elif kind in ('COS', 'SINC'):
-            put(i, 'freq', lf[2], nd)
-        elif kind in ('SIN', 'SM'):
-            put(i, 'freq', lf[2], nd)
-            put(i, 'rate', lf[3], nd)
+        for member, idx in LEAF_FIELDS[kind].items():     # (the exponent of a DOT leaf is not in the table: it stays the template's)
+            put(i, member, lf[idx], 1 if member == 'alpha' else nd)
     fields = np.stack(cols, axis=1) if cols else np.zeros((B, 0))
     return tmpl, np.asarray(offs, dtype=np.int32), np.ascontiguousarray(fields)

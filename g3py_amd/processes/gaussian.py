@@ -123,13 +123,10 @@ class GaussianProcess(EllipticalProcess):
     def _chain_rule(self, values, inputs, outputs, nat, prog, gmap, slots, alpha, d):
         """host part of d loglike: route the device's per-leaf parameter sums (`slots`) to the model's
         variables and add the O(N) location / warping terms on alpha = s K^-1 delta"""
-        from ..device import spec_leaves
-        # kernel hypers: leaf parameter slots -> the HyperVars that fed them
+        from ..device import spec_leaves, LEAF_FIELDS as fields
+        # kernel hypers: leaf parameter slots -> the HyperVars that fed them (the alpha slot of a dot leaf is its bias)
         by_name = {v.name: v for v in self.model.vars}
         refs = spec_leaves(self.f_kernel_noise.spec(_Refs(), d))
-        fields = {'SE': dict(rate=2), 'OU': dict(rate=2), 'MAT32': dict(rate=2), 'MAT52': dict(rate=2),
-                  'RQ': dict(rate=2, alpha=3), 'COS': dict(freq=2), 'SINC': dict(freq=2),
-                  'SIN': dict(freq=2, rate=3), 'SM': dict(freq=2, rate=3), 'NOISE': {}, 'WN': {}}
         for l, lf in enumerate(refs):
             nd = prog.leaf[l].ndims
             for pname, idx in dict(var=1, **fields[lf[0]]).items():
@@ -283,7 +280,7 @@ class GaussianProcess(EllipticalProcess):
 
     def _chain_rule_rows(self, values_b, X, y, nat, prog, gmap, slots, alphas, d, ok, B):
         """_chain_rule for B rows at once: slots (B, nslots), alphas (B, N); rows with ok False get no likelihood term"""
-        from ..device import spec_leaves
+        from ..device import spec_leaves, LEAF_FIELDS as fld
         by_name = {v.name: v for v in self.model.vars}
         with np.errstate(all='ignore'):
             slots = np.where(ok[:, None], slots, 0.0)
@@ -293,9 +290,6 @@ class GaussianProcess(EllipticalProcess):
             shp = tuple(by_name[name].shape)
             nat[name] = nat[name] + np.asarray(g, dtype=np.float64).reshape((B,) + shp)
         refs = spec_leaves(self.f_kernel_noise.spec(_Refs(), d))
-        fld = {'SE': dict(rate=2), 'OU': dict(rate=2), 'MAT32': dict(rate=2), 'MAT52': dict(rate=2),
-               'RQ': dict(rate=2, alpha=3), 'COS': dict(freq=2), 'SINC': dict(freq=2),
-               'SIN': dict(freq=2, rate=3), 'SM': dict(freq=2, rate=3), 'NOISE': {}, 'WN': {}}
         for l, lf in enumerate(refs):
             nd = prog.leaf[l].ndims
             for pname, idx in dict(var=1, **fld[lf[0]]).items():

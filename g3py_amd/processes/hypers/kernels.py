@@ -1,5 +1,5 @@
-"""Kernel algebra and the stationary kernel library of g3py
-(g3py/processes/hypers/kernels.py:13-79, 96-110, 192-244, 360-487), MI355X edition.
+"""Kernel algebra, the stationary kernel library and the dot-product family of g3py
+(g3py/processes/hypers/kernels.py:13-79, 82-110, 192-244, 293-487), MI355X edition.
 
 A kernel object describes a covariance function; `spec(values, d)` turns it into the plain
 nested-tuple description that `g3py_amd.device.compile_spec` lowers to a `g3_kernel_prog`,
@@ -8,7 +8,8 @@ and `cov(x1, x2=None, params=...)` evaluates it on the GPU through `g3_gram`.
 import numpy as np
 
 from . import Hypers, HyperVar, value_of
-from .metrics import Delta, Difference, ARD_L1, ARD_L2
+from .metrics import Delta, Difference, ARD_L1, ARD_L2, One, Minimum, ARD_Dot, ARD_DotBias
+from ... import _lib
 
 pi = np.pi
 
@@ -354,3 +355,85 @@ class SINC(KernelPeriodic):
 class SM(KernelPeriodic):
     """exp(-2 pi^2 sum dx^2 rate^2) prod cos(2 pi dx f) -- kernels.py:485-487"""
     kind = 'SM'
+
+
+# ---- the dot-product family (kernels.py:82-93, 293-357): non-stationary -- the value depends on x1, x2 themselves
+
+class KernelDot(Kernel):
+    """var * metric(x1, x2) -- kernels.py:82-93.  The metric decides the device leaf: ARD_Dot / ARD_DotBias -> 'DOT'
+    (var * (bias + sum_k rate_k^2 x1_k x2_k)^p), Minimum -> 'BW', One -> 'VAR'."""
+    p = 1
+
+    def __init__(self, x=None, name=None, metric=ARD_Dot, var=None):
+        Kernel.__init__(self, x, name, metric, var)
+
+    def _dot_args(self, values):
+        kind = getattr(self.metric, 'kind', None)
+        if kind not in ('dot', 'dotbias'):
+            raise _lib.G3Error('%s needs an ARD_Dot or ARD_DotBias metric, not %s' % (type(self).__name__, type(self.metric).__name__))
+        bias = value_of(self.metric.bias, values) if kind == 'dotbias' else 0.0
+        return value_of(self.var, values), value_of(self.metric.rate, values), bias
+
+    def spec(self, values, d):
+        kind = getattr(self.metric, 'kind', None)
+        if kind == 'min' and self.p == 1:
+            return ('BW', value_of(self.var, values), self.metric.dims_index(d))
+        if kind == 'one' and self.p == 1:
+            return ('VAR', value_of(self.var, values))
+        var, rate, bias = self._dot_args(values)
+        return ('DOT', var, rate, bias, int(self.p), self.metric.dims_index(d))
+
+
+class BW(KernelDot):
+    """Brownian: var * prod_k min(x1_k, x2_k) -- kernels.py:293-295"""
+
+    def __init__(self, x=None, name=None, metric=Minimum, var=None):
+        KernelDot.__init__(self, x, name, metric, var)
+
+
+class VAR(KernelDot):
+    """the constant var -- kernels.py:298-308"""
+
+    def __init__(self, x=None, name=None, metric=One, var=None):
+        KernelDot.__init__(self, x, name, metric, var)
+
+
+class NIL(KernelDot):
+    """zero -- kernels.py:311-321; lowered to a 'VAR' leaf with var = 0 (no kind of its own)"""
+
+    def __init__(self, x=None, name=None, metric=One, var=1):
+        KernelDot.__init__(self, x, name, metric, var)
+
+    def spec(self, values, d):
+        return ('VAR', 0.0)
+
+
+class LIN(KernelDot):
+    """var * (bias + sum_k rate_k^2 x1_k x2_k), var = 1 unless given -- kernels.py:324-326"""
+
+    def __init__(self, x=None, name=None, metric=ARD_DotBias, var=1):
+        KernelDot.__init__(self, x, name, metric, var)
+
+
+class POL(KernelDot):
+    """var * (bias + sum_k rate_k^2 x1_k x2_k)**p -- kernels.py:329-341.  p is structure (an integer 1 <= p <= 8,
+    evaluated by repeated multiplication: the base may be negative), not a hyper-parameter."""
+
+    def __init__(self, x=None, p=2, name=None, metric=ARD_DotBias, var=1):
+        KernelDot.__init__(self, x, name, metric, var)
+        if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= _lib.G3_DOT_MAXP:
+            raise _lib.G3Error('POL: the exponent p must be an integer with 1 <= p <= %d (got %r); it is a structural '
+                               'constant evaluated by repeated multiplication' % (_lib.G3_DOT_MAXP, p))
+        self.p = int(p)
+
+
+class NN(KernelDot):
+    """var * arcsin(2 m12 / ((1 + 2 m11)(1 + 2 m22))), m = ARD_DotBias -- NN.__call__, kernels.py:348-349, applied
+    pointwise in the square and the cross case (the reference's NN.cov overrides, kernels.py:351-357, do not broadcast)"""
+
+    def __init__(self, x=None, name=None, metric=ARD_DotBias, var=None):
+        KernelDot.__init__(self, x, name, metric, var)
+
+    def spec(self, values, d):
+        var, rate, bias = self._dot_args(values)
+        return ('NN', var, rate, bias, self.metric.dims_index(d))

@@ -43,7 +43,7 @@ typedef struct g3_ctx g3_ctx;
 typedef enum { G3_F64 = 0, G3_F32 = 1 } g3_dtype;
 
 /* ---- kernel description -------------------------------------------------------------
- * A covariance function is passed as a sum of products of stationary "leaf" kernels
+ * A covariance function is passed as a sum of products of "leaf" kernels (stationary ones and the dot-product family)
  *      K(x1, x2) = shift + sum_p coef_p * prod_{t in p} leaf_t(x1, x2)
  * which is what any tree of g3py's KernelSum / KernelProd / KernelScale / KernelShift
  * (g3py/processes/hypers/kernels.py:192-244) over leaf kernels expands to.
@@ -67,17 +67,31 @@ typedef enum {
   G3_K_SINC = 7,  /* var*prod_k [dx!=0 ? sin(2pi^2 dx f)/(2pi^2 f dx):1] kernels.py:475-482 */
   G3_K_SM = 8,    /* var*exp(-2pi^2 sum dx^2 rate^2)*prod cos(2pi dx f)  kernels.py:485-487 */
   G3_K_NOISE = 9, /* square: var*I ; cross: 0                            kernels.py:360-371 */
-  G3_K_WN = 10    /* square: var*I ; cross: var*#{k: dx_k==0}            kernels.py:374-385, metrics.py:30-35 */
+  G3_K_WN = 10,   /* square: var*I ; cross: var*#{k: dx_k==0}            kernels.py:374-385, metrics.py:30-35 */
+  /* ---- the dot-product family: values depend on x1, x2 themselves, not on x1 - x2; square and cross case use the same
+   * pair formula and the diagonal K(x, x) varies from point to point.  m(x1, x2) = bias + sum_k rate_k^2 x1_k x2_k
+   * (ARD_DotBias, metrics.py:119-131; ARD_Dot, metrics.py:111-113, is bias = 0).  `bias` lives in `alpha` (gradient slot
+   * g3_grad_map.alpha[l]); the other fields of a leaf are unused unless named. */
+  G3_K_DOT = 11,  /* var*m(x1,x2)^p : KernelDot (p=1, bias=0) kernels.py:82-93, LIN (p=1) :324-326, POL :329-341.  p is
+                     STRUCTURE, not a hyper-parameter: an integer 1 <= p <= G3_DOT_MAXP held as a double in freq[0]
+                     (no gradient slot; the *_fields entry points refuse its offset); evaluated by repeated multiplication */
+  G3_K_NN = 12,   /* var*asin(2 m12 / ((1 + 2 m11)(1 + 2 m22))), m11 = m(x1,x1), m22 = m(x2,x2): NN.__call__,
+                     kernels.py:348-349, pointwise for the square and the cross case (no square root, as written) */
+  G3_K_BW = 13,   /* var*prod_k min(x1_k, x2_k)                          kernels.py:293-295, metrics.py:54-56 */
+  G3_K_VAR = 14   /* var (constant)                                      kernels.py:298-308; NIL (kernels.py:311-321) is
+                     passed as a G3_K_VAR leaf with var = 0 */
 } g3_kind;
+#define G3_K_LAST G3_K_VAR
+#define G3_DOT_MAXP 8  /* largest exponent of a G3_K_DOT leaf */
 
 typedef struct {
   int32_t kind;             /* g3_kind */
   int32_t ndims;            /* number of input columns used (x[:, dims], hypers/__init__.py:55-83) */
   int32_t dims[G3_MAXD];    /* the column indices */
   double var;
-  double alpha;             /* RQ only */
+  double alpha;             /* RQ: alpha; G3_K_DOT / G3_K_NN: bias */
   double rate[G3_MAXD];     /* per used column */
-  double freq[G3_MAXD];     /* periodic family */
+  double freq[G3_MAXD];     /* periodic family; G3_K_DOT: freq[0] = the exponent p */
 } g3_leaf;
 
 typedef struct {
@@ -302,7 +316,8 @@ int g3_gp_factor_batched(g3_ctx* ctx, const g3_kernel_prog* progs_host, int batc
 /* The same sweep with the members' programs given as ONE template plus what differs: member b is
  * the template with the double at byte offset offsets_host[i] of g3_kernel_prog replaced by
  * fields_host[b * nfield + i] (i < nfield <= G3_MAX_FIELDS).  Offsets must name double members
- * (shift, leaf var / alpha / rate[k] / freq[k], product coef).  The members are expanded on the
+ * (shift, leaf var / alpha / rate[k] / freq[k], product coef), except freq[0] of a G3_K_DOT leaf of the template: the
+ * exponent is structure and the same for every member.  The members are expanded on the
  * device, so a chain row costs nfield doubles of packing and PCIe instead of a 6 KB program --
  * what lets logp_chain / fixed_logp (stochastic.py:515-532) keep up with the one-workgroup-per-
  * member evaluation at N <= 256.  Members that fail the first factorisation are rebuilt on the
@@ -324,7 +339,8 @@ int g3_gp_factor_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, in
  * g3_grad_map tells the device where each parameter of each leaf of a g3_kernel_prog goes in
  * the output vector: slot index, or -1 to skip; `rate` / `freq` name the first of `ndims`
  * consecutive slots.  g3_grad_layout fills the standard map (every parameter of every leaf, in
- * leaf order: var, [alpha], [freq...], [rate...] as the leaf kind has them). */
+ * leaf order: var, [alpha], [freq...], [rate...] as the leaf kind has them; G3_K_DOT and G3_K_NN: var, alpha (the
+ * bias), rate[k]; G3_K_BW and G3_K_VAR: var). */
 #define G3_GRAD_MAXSLOTS (G3_MAXLEAF * (2 + 2 * G3_MAXD))
 typedef struct g3_grad_map {
   int32_t nslots;
