@@ -113,6 +113,10 @@ _SIGS = {
                                      _I64, C.c_int, _P, _I64, _I64, _P, _P, C.POINTER(C.c_double)], C.c_int),
     'g3_gp_cross': ([_P, C.POINTER(KernelProg), _P, _I64, _I64, _P, _I64, _I64, C.c_int, _P, _I64, _P, _P,
                      C.c_int, _P, _I64, _P, _P], C.c_int),
+    'g3_gp_cross_batched': ([_P, C.POINTER(KernelProg), C.c_int, _P, _I64, _I64, _P, _I64, _I64, C.c_int, _P, _I64, _I64,
+                             _P, _P, C.c_int, _P, _P, _P], C.c_int),
+    'g3_gp_cross_batched_fields': ([_P, C.POINTER(KernelProg), C.c_int, _P, _P, C.c_int, _P, _I64, _I64, _P, _I64, _I64,
+                                    C.c_int, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P], C.c_int),
     'g3_gp_sample': ([_P, _P, _I64, _I64, _P, _P, _I64, C.c_int, _P], C.c_int),
     'g3_grad_layout': ([C.POINTER(KernelProg), C.POINTER(GradMap)], C.c_int),
     'g3_potri': ([_P, _P, _I64, _I64, _P, C.c_int, _P, _I64, _P, _I64], C.c_int),

@@ -938,6 +938,12 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
 // many hyper-parameter vectors on the same inputs.  All `batch` covariances are built by one
 // Gram launch (grid.z) and factored by ONE sweep whose GEMM / diagonal-block launches carry the
 // batch in grid.y, so a problem too small to fill 256 CUs on its own still does.
+//
+// ctx->bbuf is ONE buffer shared by the batched entry points: g3_gp_factor_batched keeps its device programs, statistics
+// and cooperative-kernel control words in it, g3_gp_cross_batched its device programs and, for Np > 1024, one member's V.
+// Each call lays it out afresh from offset 0 and has queued its last use on ctx->stream when it returns, so the next call's
+// writes, on the same stream, come after.  Growing it frees (hipFree waits for the device) and reallocates, so nothing may
+// keep a pointer into it across calls or across a second ensure_bbuf within one call.
 static int ensure_bbuf(g3_ctx* ctx, size_t bytes) {
   if (ctx->bbuf_bytes >= bytes) return G3_OK;
   if (ctx->bbuf) (void)hipFree(ctx->bbuf);
@@ -1248,6 +1254,154 @@ extern "C" int g3_gp_cross(g3_ctx* ctx, const g3_kernel_prog* prog, const void* 
     g3i_prof_end(ctx, pr);
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------------------
+// g3_gp_cross for every member of a chain after ONE g3_gp_factor_batched sweep: what the reference's average / particles
+// (g3py/bayesian/models.py:489-543) get from a Python loop of single predictions over the rows of a trace.  The members'
+// rectangular cross-Gram blocks come from one Gram launch with the member in grid.z (generated kernel or interpreter), the
+// block forward solves and the row sums from one launch of g3_crossb.hip with the member in grid.y; V never leaves the
+// library.  The cross-Gram workspace is the context's, at most G3_CROSSB_WORK bytes of it: longer chains go through in
+// several (Gram, solve) launch pairs.
+#define G3_CROSSB_WORK ((size_t)256 << 20)
+static int gp_cross_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, const void* Xs, int64_t M, int64_t ldxs,
+                                 const void* X, int64_t N, int64_t ldx, int d, const void* L, int64_t ldl, int64_t kstride,
+                                 const void* invd, const void* a, g3_dtype dt, void* mu, void* ss, void* kdiag) {
+  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
+  if (!Xs) return -4;
+  if (M <= 0) return -5;
+  if (!X) return -7;
+  if (N <= 0) return -8;
+  if (d < 1 || d > G3_MAXCOLS) return -10;
+  if (ldxs < d) return -6;
+  if (ldx < d) return -9;
+  if (dt != G3_F64 && dt != G3_F32) return -16;
+  g3_kernel_prog first;
+  mp.member(0, &first);
+  if (mp.progs) {
+    for (int b = 0; b < batch; ++b)
+      if (g3i_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return -2;
+  } else if (g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(&first, d)) {
+    return -2;
+  }
+  const int64_t Np = g3_roundup(N, G3_LB), Mp = g3_roundup(M, 128);
+  const size_t es = g3_esize(dt);
+  const int64_t al = 16 / (int64_t)es;
+  const bool solve = mu || ss;
+  if (solve) {
+    if (!L) return -11;
+    if (ldl < Np || ldl % al) return -12;
+    if (kstride < Np * ldl || kstride % al) return -13;
+    if (!invd) return -14;
+    if (mu && !a) return -15;
+  }
+  if (!solve && !kdiag) return G3_OK;
+  // device copies of the members' programs: whole programs, or -- as g3_gp_factor_batched_fields does -- the template and the
+  // batch x nfield doubles that differ, expanded on the device (a chain row costs nfield doubles of PCIe, not a 6 KB program).
+  // Members beyond the one-launch solve keep their V (Mp x Np) behind the programs in the same context buffer.
+  const bool big = solve && Np > 1024;
+  const size_t pbytes = (size_t)batch * sizeof(g3_kernel_prog);
+  const size_t fbytes = mp.progs ? 0 : (size_t)batch * mp.nfield * sizeof(double);
+  const size_t obytes = mp.progs ? 0 : (((size_t)mp.nfield * sizeof(int32_t) + 15) & ~(size_t)15);
+  const size_t head = (pbytes + (mp.progs ? 0 : sizeof(g3_kernel_prog)) + fbytes + obytes + 255) & ~(size_t)255;
+  int rc = ensure_bbuf(ctx, head + (big ? (size_t)Mp * Np * es : 0));
+  if (rc) return rc;
+  g3_kernel_prog* dprogs = (g3_kernel_prog*)ctx->bbuf;
+  if (mp.progs) {
+    G3_HIP(hipMemcpyAsync(dprogs, mp.progs, pbytes, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    g3_kernel_prog* dtmpl = (g3_kernel_prog*)((char*)dprogs + pbytes);
+    double* dfields = (double*)(dtmpl + 1);
+    int32_t* doffs = (int32_t*)((char*)dfields + fbytes);
+    G3_HIP(hipMemcpyAsync(dtmpl, mp.tmpl, sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
+    if (mp.nfield) {
+      G3_HIP(hipMemcpyAsync(dfields, mp.fields, fbytes, hipMemcpyHostToDevice, ctx->stream));
+      G3_HIP(hipMemcpyAsync(doffs, mp.offs, (size_t)mp.nfield * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    hipLaunchKernelGGL(expand_progs_kernel, dim3(batch), dim3(256), 0, ctx->stream, dprogs, dtmpl, dfields, doffs, mp.nfield);
+    G3_LAUNCH_CHECK();
+  }
+  G3_HIP(hipStreamSynchronize(ctx->stream));          // the host arrays are borrowed for the call only
+  if (kdiag) {
+    rc = g3i_gram_diag_batched(ctx, dprogs, batch, Xs, M, ldxs, d, dt, kdiag, Mp);
+    if (rc) return rc;
+  }
+  if (!solve) return G3_OK;
+  const int64_t wstride = Np * G3_LB;
+  if (!big) {
+    const size_t per = (size_t)Mp * Np * es;
+    int64_t cb = (int64_t)(G3_CROSSB_WORK / per);
+    cb = cb < 1 ? 1 : (cb > batch ? batch : cb);
+    rc = g3i_ensure_work(ctx, (size_t)cb * per);
+    if (rc) return rc;
+    for (int64_t b0 = 0; b0 < batch; b0 += cb) {
+      const int nb = (int)(batch - b0 < cb ? batch - b0 : cb);
+      // Ks_b = tt_to_num(cov_b(Xs, X))  (elliptical.py:78-79): NOISE contributes nothing to a cross block
+      int pr = g3i_prof_begin(ctx, G3_TAG_CROSS_GRAM, (double)nb * ((double)(N + M) * d + (double)N * M) * es);
+      rc = g3i_gram_rect_batched(ctx, dprogs + b0, &first, nb, Xs, M, ldxs, X, N, ldx, d, dt, ctx->work, Np, Mp * Np, Mp, Np,
+                                 G3_GRAM_SCRUB, 0);
+      g3i_prof_end(ctx, pr);
+      if (rc) return rc;
+      pr = g3i_prof_begin(ctx, G3_TAG_TRSM, (double)nb * (double)N * N * M);
+      rc = g3i_cross_solve_batched(ctx, ctx->work, Mp * Np, (const char*)L + (size_t)b0 * kstride * es, ldl, kstride,
+                                   (const char*)invd + (size_t)b0 * wstride * es, wstride,
+                                   a ? (const char*)a + (size_t)b0 * Np * es : nullptr, Np,
+                                   mu ? (char*)mu + (size_t)b0 * Mp * es : nullptr, ss ? (char*)ss + (size_t)b0 * Mp * es : nullptr,
+                                   Mp, Mp, N, Np, nb, dt);
+      g3i_prof_end(ctx, pr);
+      if (rc) return rc;
+    }
+    return G3_OK;
+  }
+  // members beyond the one-launch solve: the single-member path (Gram, recursive solve, row sums) once per member
+  void* V = (char*)ctx->bbuf + head;
+  for (int b = 0; b < batch; ++b) {
+    g3_kernel_prog mine;
+    mp.member(b, &mine);
+    rc = g3_gram(ctx, &mine, Xs, M, ldxs, X, N, ldx, d, dt, V, Np, Mp, Np, G3_GRAM_SCRUB);
+    if (!rc) rc = g3i_reset_info(ctx);
+    if (!rc) rc = g3i_trsm_rlt(ctx, (const char*)L + (size_t)b * kstride * es, Np, ldl, V, Mp, Np, dt,
+                               (const char*)invd + (size_t)b * wstride * es);
+    if (!rc) rc = rows_dot_ss_launch(ctx, V, M, N, Np, a ? (const char*)a + (size_t)b * Np * es : nullptr, dt,
+                                     mu ? (char*)mu + (size_t)b * Mp * es : nullptr, ss ? (char*)ss + (size_t)b * Mp * es : nullptr);
+    if (rc) return rc;
+  }
+  return G3_OK;
+}
+
+extern "C" int g3_gp_cross_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const void* Xs, int64_t M, int64_t ldxs,
+                                   const void* X, int64_t N, int64_t ldx, int d, const void* L, int64_t ldl, int64_t kstride,
+                                   const void* invd, const void* a, g3_dtype dt, void* mu, void* ss, void* kdiag) {
+  if (!ctx) return -1;
+  g3_dev_guard _dg(ctx);
+  if (!progs) return -2;
+  MemberProgs mp;
+  mp.progs = progs;
+  return gp_cross_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, mu, ss, kdiag);
+}
+
+// The members as g3_gp_factor_batched_fields takes them: template + per-member doubles, expanded on the device by the same
+// kernel, so the two forms hand the launches the same programs and give the same bits.
+extern "C" int g3_gp_cross_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl, int batch, const double* fields,
+                                          const int32_t* offsets, int nfield, const void* Xs, int64_t M, int64_t ldxs,
+                                          const void* X, int64_t N, int64_t ldx, int d, const void* L, int64_t ldl,
+                                          int64_t kstride, const void* invd, const void* a, g3_dtype dt, void* mu, void* ss,
+                                          void* kdiag) {
+  if (!ctx) return -1;
+  g3_dev_guard _dg(ctx);
+  if (!tmpl) return -2;
+  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
+  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
+  if (nfield && (!fields || !offsets)) return -4;
+  for (int i = 0; i < nfield; ++i)
+    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
+  MemberProgs mp;
+  mp.tmpl = tmpl;
+  mp.fields = fields;
+  mp.offs = offsets;
+  mp.nfield = nfield;
+  const int rc = gp_cross_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, mu, ss, kdiag);
+  return (rc <= -4 && rc >= -19) ? rc - 3 : rc;
 }
 
 

@@ -269,8 +269,10 @@ gram_kernel(const g3_kernel_prog* __restrict__ prog, SeParams<T, D> se, const T*
 
 template <typename T>
 __global__ void gram_diag_kernel(const g3_kernel_prog* __restrict__ prog, const T* __restrict__ X,
-                                 int64_t n, int64_t ldx, int d, T* __restrict__ out) {
-  // diag(Kernel.cov(X)): the square-case diagonal, so NOISE / WN contribute
+                                 int64_t n, int64_t ldx, int d, T* __restrict__ out, int64_t ostride) {
+  // diag(Kernel.cov(X)): the square-case diagonal, so NOISE / WN contribute; grid.y = batch member (its program, its row of out)
+  prog += blockIdx.y;
+  out += (int64_t)blockIdx.y * ostride;
   extern __shared__ __attribute__((aligned(16))) char smem_g[];
   T* xs = reinterpret_cast<T*>(smem_g);
   const int dp = d | 1;
@@ -279,6 +281,20 @@ __global__ void gram_diag_kernel(const g3_kernel_prog* __restrict__ prog, const 
   if (i < n)
     for (int c = 0; c < d; ++c) xi[c] = X[i * ldx + c];
   if (i < n) out[i] = prog_eval<T>(prog, xi, xi, true, true);
+}
+
+// diag(K_b(X)) for `batch` members (device programs dprogs[b]) into out + b * ostride: g3_gram_diag with the member in grid.y
+int g3i_gram_diag_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, int batch, const void* X, int64_t n, int64_t ldx, int d,
+                          g3_dtype dt, void* out, int64_t ostride) {
+  const dim3 grid((unsigned)((n + 63) / 64), (unsigned)batch);
+  if (dt == G3_F64)
+    hipLaunchKernelGGL((gram_diag_kernel<double>), grid, dim3(64), 64 * (d | 1) * sizeof(double), ctx->stream, dprogs,
+                       (const double*)X, n, ldx, d, (double*)out, ostride);
+  else
+    hipLaunchKernelGGL((gram_diag_kernel<float>), grid, dim3(64), 64 * (d | 1) * sizeof(float), ctx->stream, dprogs,
+                       (const float*)X, n, ldx, d, (float*)out, ostride);
+  G3_LAUNCH_CHECK();
+  return G3_OK;
 }
 
 int g3i_upload_prog(g3_ctx* ctx, const g3_kernel_prog* prog, int /*slot*/, const g3_kernel_prog** dptr) {
@@ -391,14 +407,18 @@ static int gram_t(g3_ctx* ctx, const g3_kernel_prog* prog, const T* X1, int64_t 
   return G3_OK;
 }
 
-// `batch` square Gram matrices of the same inputs, member b from dprogs[b] (device array, all of
-// one structure) into K + b * kstride: the generic kernel with grid.z = batch
-int g3i_gram_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_prog* first_host, int batch,
-                     const void* X, int64_t n, int64_t ldx, int d, g3_dtype dt, void* K, int64_t ldk,
-                     int64_t kstride, int64_t npad, unsigned flags) {
-  dim3 grid = gram_grid(npad, npad, flags);
+// `batch` Gram matrices of the same inputs, member b from dprogs[b] (device array, all of one structure) into
+// K + b * kstride: the generated kernel or the interpreter with grid.z = batch.  sym = 1: the square covariance of X1 (X2
+// repeats it; NOISE / WN on the diagonal); sym = 0: the rectangular cross block K_b(X1, X2) of a chain's prediction
+// (g3_gp_cross_batched) -- the pair formulas of the dot-product family (NN's per-point terms, POL's structural exponent)
+// are the same in both.  The compile-time table (gram_kernel<T, D, FK, PK>) takes its parameters by value and serves one
+// member per launch, so it is not used here.
+int g3i_gram_rect_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_prog* first_host, int batch, const void* X1,
+                          int64_t n1, int64_t ldx1, const void* X2, int64_t n2, int64_t ldx2, int d, g3_dtype dt, void* K,
+                          int64_t ldk, int64_t kstride, int64_t n1pad, int64_t n2pad, unsigned flags, int sym) {
+  dim3 grid = gram_grid(n1pad, n2pad, flags);
   grid.z = (unsigned)batch;
-  if (g3i_gram_jit(ctx, first_host, dprogs, batch, X, n, ldx, X, n, ldx, d, dt, K, ldk, npad, npad, flags, 1, kstride, (int64_t)0, grid) == 0)
+  if (g3i_gram_jit(ctx, first_host, dprogs, batch, X1, n1, ldx1, X2, n2, ldx2, d, dt, K, ldk, n1pad, n2pad, flags, sym, kstride, (int64_t)0, grid) == 0)
     return G3_OK;
   ctx->gram_paths[2] += 1;
   int ntrig = prog_trig_pairs(first_host);
@@ -407,17 +427,23 @@ int g3i_gram_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_
     const size_t lds = (GT + GTN) * ((d | 1) + (ntrig ? 2 * ntrig + 1 : 0)) * sizeof(double);
     SeParams<double, 1> dummy{};
     hipLaunchKernelGGL((gram_kernel<double, 1, -1, -1>), grid, dim3(256), lds, ctx->stream, dprogs, dummy,
-                       (const double*)X, n, ldx, (const double*)X, n, ldx, d, (double*)K, ldk, npad, npad, flags, 1,
+                       (const double*)X1, n1, ldx1, (const double*)X2, n2, ldx2, d, (double*)K, ldk, n1pad, n2pad, flags, sym,
                        ntrig, kstride, (int64_t)0);
   } else {
     const size_t lds = (GT + GTN) * ((d | 1) + (ntrig ? 2 * ntrig + 1 : 0)) * sizeof(float);
     SeParams<float, 1> dummy{};
     hipLaunchKernelGGL((gram_kernel<float, 1, -1, -1>), grid, dim3(256), lds, ctx->stream, dprogs, dummy,
-                       (const float*)X, n, ldx, (const float*)X, n, ldx, d, (float*)K, ldk, npad, npad, flags, 1,
+                       (const float*)X1, n1, ldx1, (const float*)X2, n2, ldx2, d, (float*)K, ldk, n1pad, n2pad, flags, sym,
                        ntrig, kstride, (int64_t)0);
   }
   G3_LAUNCH_CHECK();
   return G3_OK;
+}
+
+int g3i_gram_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_prog* first_host, int batch,
+                     const void* X, int64_t n, int64_t ldx, int d, g3_dtype dt, void* K, int64_t ldk,
+                     int64_t kstride, int64_t npad, unsigned flags) {
+  return g3i_gram_rect_batched(ctx, dprogs, first_host, batch, X, n, ldx, X, n, ldx, d, dt, K, ldk, kstride, npad, npad, flags, 1);
 }
 
 int g3i_validate_prog(const g3_kernel_prog* p, int d);
@@ -500,15 +526,7 @@ extern "C" int g3_gram_diag(g3_ctx* ctx, const g3_kernel_prog* prog, const void*
   const g3_kernel_prog* dprog;
   int rc = g3i_upload_prog(ctx, prog, 1, &dprog);
   if (rc) return rc;
-  const unsigned nb = (unsigned)((n + 63) / 64);
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((gram_diag_kernel<double>), dim3(nb), dim3(64), 64 * (d | 1) * sizeof(double),
-                       ctx->stream, dprog, (const double*)X, n, ldx, d, (double*)diag);
-  else
-    hipLaunchKernelGGL((gram_diag_kernel<float>), dim3(nb), dim3(64), 64 * (d | 1) * sizeof(float),
-                       ctx->stream, dprog, (const float*)X, n, ldx, d, (float*)diag);
-  G3_LAUNCH_CHECK();
-  return G3_OK;
+  return g3i_gram_diag_batched(ctx, dprog, 1, X, n, ldx, d, dt, diag, 0);
 }
 
 extern "C" int g3_gram_path_stats(g3_ctx* ctx, double out_host[3]) {

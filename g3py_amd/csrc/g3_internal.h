@@ -222,6 +222,17 @@ int g3i_upload_prog(g3_ctx* ctx, const g3_kernel_prog* prog, int slot, const g3_
 int g3i_gram_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_prog* first_host, int batch,
                      const void* X, int64_t n, int64_t ldx, int d, g3_dtype dt, void* K, int64_t ldk,
                      int64_t kstride, int64_t npad, unsigned flags);
+// the same launch for the rectangular cross block K_b(X1, X2) (sym = 0) or the square covariance (sym = 1, X2 = X1)
+int g3i_gram_rect_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_prog* first_host, int batch, const void* X1,
+                          int64_t n1, int64_t ldx1, const void* X2, int64_t n2, int64_t ldx2, int d, g3_dtype dt, void* K,
+                          int64_t ldk, int64_t kstride, int64_t n1pad, int64_t n2pad, unsigned flags, int sym);
+// diag(K_b(X)) per member (device programs) into out + b * ostride
+int g3i_gram_diag_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, int batch, const void* X, int64_t n, int64_t ldx, int d,
+                          g3_dtype dt, void* out, int64_t ostride);
+// batched posterior cross solve (g3_crossb.hip): Ks = batch x Mp x Np cross-Gram blocks (consumed), mu / ss batch x ostride
+int g3i_cross_solve_batched(g3_ctx* ctx, void* Ks, int64_t sstride, const void* L, int64_t ldl, int64_t lstride, const void* W,
+                            int64_t wstride, const void* a, int64_t astride, void* mu, void* ss, int64_t ostride, int64_t Mp,
+                            int64_t N, int64_t Np, int batch, g3_dtype dt);
 int g3i_validate_prog(const g3_kernel_prog* p, int d);
 // the Gram kernel generated for prog's structure (g3_gram_jit.hip); 0 = launched, 1 = none (the caller interprets)
 int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_prog* prog_dev, int batch, const void* X1, int64_t n1,

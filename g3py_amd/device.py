@@ -338,6 +338,37 @@ class Device:
                                   mu.ptr if mu is not None else None, ss.ptr if ss is not None else None)
         _check(self, rc, 'g3_gp_cross')
 
+    @staticmethod
+    def _ptr(a):
+        return a.ptr if a is not None else None
+
+    def gp_cross_batched(self, progs, Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag):
+        """after gp_factor_batched on the same buffers: per member b, mu[b] = V_b a_b, ss[b] = |rows of V_b|^2 for
+        V_b = K_b(Xs, X) L_b^-T and kdiag[b] = diag K_b(Xs, Xs), each a device (B, roundup(M, 128)) matrix or None.
+        With mu and ss both None the factor buffers K, W, a may be None too (the prior needs no factorisation)."""
+        B = len(progs)
+        arr = progs if isinstance(progs, C.Array) else (_lib.KernelProg * B)(*progs)
+        out = next(o for o in (mu, ss, kdiag) if o is not None)
+        rc = self.lib.g3_gp_cross_batched(self.ctx, arr, B, Xs.ptr, M, Xs.ld, X.ptr, N, X.ld, d, self._ptr(K),
+                                          K.ld if K is not None else 0, kstride, self._ptr(W), self._ptr(a),
+                                          _lib.dtype_code(out.dtype), self._ptr(mu), self._ptr(ss), self._ptr(kdiag))
+        _check(self, rc, 'g3_gp_cross_batched')
+
+    def gp_cross_batched_fields(self, tmpl, offsets, fields, Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag):
+        """gp_cross_batched for members given as template + fields (see compile_spec_rows), after
+        gp_factor_batched_fields on the same buffers"""
+        fields = np.ascontiguousarray(fields, dtype=np.float64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        B, nf = fields.shape
+        if len(offsets) != nf:
+            raise G3Error('gp_cross_batched_fields: %d offsets for %d fields' % (len(offsets), nf))
+        out = next(o for o in (mu, ss, kdiag) if o is not None)
+        rc = self.lib.g3_gp_cross_batched_fields(self.ctx, C.byref(tmpl), B, fields.ctypes.data, offsets.ctypes.data, nf,
+                                                 Xs.ptr, M, Xs.ld, X.ptr, N, X.ld, d, self._ptr(K),
+                                                 K.ld if K is not None else 0, kstride, self._ptr(W), self._ptr(a),
+                                                 _lib.dtype_code(out.dtype), self._ptr(mu), self._ptr(ss), self._ptr(kdiag))
+        _check(self, rc, 'g3_gp_cross_batched_fields')
+
     def gp_dlogp_batched(self, progs, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha):
         """after gp_factor_batched: per member K^-1, alpha and the kernel-parameter sums; returns (B, nslots)"""
         B = len(progs)

@@ -183,19 +183,29 @@ class GaussianProcess(EllipticalProcess):
         gradient terms to `nat` here (rows with ok False: none)"""
         return None
 
-    def _chain_workspace(self, batch, Np, grad):
-        """device buffers of logp_chain / dlogp_chain, kept between calls (samplers and optimisers evaluate chain after
-        chain on one data set; a GB-sized hipMalloc + hipFree per call costs more than the evaluation: 250 - 390 ms spikes
-        against 7 ms).  One workspace serves both: it only grows (more members, or the two extra matrices of the gradient)
-        and is replaced when the padded size or the dtype changes."""
+    def _chain_workspace(self, batch, Np, grad, pred=0):
+        """device buffers of logp_chain / dlogp_chain / predict_chain, kept between calls (samplers and optimisers evaluate
+        chain after chain on one data set; a GB-sized hipMalloc + hipFree per call costs more than the evaluation: 250 - 390 ms
+        spikes against 7 ms).  One workspace serves all three: it only grows (more members, the two extra matrices of the
+        gradient, the three `pred`-wide result vectors per member of a prediction) and is replaced when the padded size or
+        the dtype changes."""
         ws = getattr(self, '_chain_ws', None)
         same = ws is not None and ws['Np'] == int(Np) and ws['dtype'] == self.dtype.str
         if same and ws['cap'] >= batch and (ws['grad'] or not grad):
+            if ws['pred'] < pred:     # a wider query set: only the three result vectors grow, the matrices stay
+                dev = self.device
+                for k in ('mu', 'ss', 'kd'):
+                    if ws[k] is not None:
+                        ws['bufs'].remove(ws[k])
+                        ws[k].free()
+                    ws[k] = dev.alloc(ws['cap'], int(pred), self.dtype)
+                    ws['bufs'].append(ws[k])
+                ws['pred'] = int(pred)
             return ws
-        cap, grad = int(batch), bool(grad)
+        cap, grad, pred = int(batch), bool(grad), int(pred)
         if ws is not None:
             if same:                 # grow, never shrink: logp_chain and dlogp_chain alternate inside one optimiser
-                cap, grad = max(cap, ws['cap']), grad or ws['grad']
+                cap, grad, pred = max(cap, ws['cap']), grad or ws['grad'], max(pred, ws['pred'])
             for b in ws['bufs']:
                 b.free()
         dev = self.device
@@ -203,10 +213,120 @@ class GaussianProcess(EllipticalProcess):
         mats = [dev.alloc(cap * (Np + _lib.G3_RHS_PAD), Np, self.dtype) for _ in range(n3)]
         W = dev.alloc(cap * Np, _lib.G3_PAD, self.dtype)
         vecs = [dev.alloc(cap, Np, self.dtype) for _ in range(2 if grad else 1)]
-        ws = dict(Np=int(Np), dtype=self.dtype.str, cap=cap, grad=grad, K=mats[0], Y=mats[1] if grad else None,
-                  Ki=mats[2] if grad else None, W=W, a=vecs[0], al=vecs[1] if grad else None, bufs=mats + [W] + vecs)
+        outs = [dev.alloc(cap, pred, self.dtype) for _ in range(3)] if pred else [None] * 3
+        ws = dict(Np=int(Np), dtype=self.dtype.str, cap=cap, grad=grad, pred=pred, K=mats[0], Y=mats[1] if grad else None,
+                  Ki=mats[2] if grad else None, W=W, a=vecs[0], al=vecs[1] if grad else None, mu=outs[0], ss=outs[1],
+                  kd=outs[2], bufs=mats + [W] + vecs + [o for o in outs if o is not None])
         self._chain_ws = ws
         return ws
+
+    # ---- posterior prediction over a chain (models.py:489-519: a loop of single predictions in the reference)
+    _CHAIN_PREDICT = True
+
+    def _chain_predict_batched(self):
+        """the batched block path serves the plain Gaussian process on one GPU: a warping needs its row form of the
+        forward map and of the Gauss-Hermite moments, the Student-t process its per-row scale, a distributed process the
+        multi-GPU driver -- those take the loop of single predictions"""
+        from .hypers.mappings import Identity
+        return bool(type(self)._CHAIN_PREDICT and self._dist is None and type(self.f_mapping) is Identity)
+
+    def _predict_chain_blocks(self, rows, space, inputs, outputs, switches, noise, prior, batch):
+        """predict_chain for a plain Gaussian process: per block of `batch` rows ONE batched factorisation
+        (g3_gp_factor_batched_fields) and ONE batched cross solve (g3_gp_cross_batched_fields: rectangular Gram with the
+        member in the grid, block forward solve with the row sums fused, diag K(space) per member); the host side is array
+        arithmetic over the rows, formula by formula what th_location / th_kernel_diag / quantiler do for one row."""
+        from ..libs import DictObj
+        dev = self.device
+        t = self.dtype.type
+        big = t(np.float32(1e10))
+        S = self._x(self.space if space is None else space)
+        X = self._x(self.inputs if inputs is None else inputs)
+        y = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
+        n_rows, M = len(rows), S.shape[0]
+        N, d = X.shape
+        Np, Mp = _lib.roundup(N), _lib.roundup(M, _lib.G3_RHS_PAD)
+        need_loc = switches['mean'] or switches['median'] or switches['quantiles']
+        need_var = switches['var'] or switches['std'] or switches['quantiles']
+        keys = self._predict_chain_keys(switches)
+        out = DictObj((k, np.empty((n_rows, M), dtype=self.dtype)) for k in keys)
+        kstride = (Np + _lib.G3_RHS_PAD) * Np
+        if batch is None:
+            # per member: factor + right-hand-side block, block inverses, a, and the three result vectors; the cross-Gram
+            # blocks live in the library's own workspace (at most 256 MB of it, g3_gp_cross_batched)
+            per = (3 * Mp if prior else kstride + Np * _lib.G3_PAD + Np + 3 * Mp) * self.dtype.itemsize
+            batch = int((4e9 - 2 ** 28) // per)
+        batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
+        Sd = dev.upload(S)
+        kern_c = self.f_kernel_noise if noise else self.f_kernel         # elliptical.py:78-79
+        if prior:
+            Xd, K, W, a, mu, ss = Sd, None, None, None, None, None
+            kd = dev.alloc(batch, Mp, self.dtype) if need_var else None
+        else:
+            Xd = dev.upload(X)
+            ws = self._chain_workspace(batch, Np, False, pred=Mp)
+            K, W, a = ws['K'], ws['W'], ws['a']
+            # the library writes the members' results roundup(M, 128) apart: views of that shape on the (wider) buffers
+            mu, ss, kd = (dev.wrap(ws[k].ptr, batch, Mp, Mp, self.dtype, keep=ws[k]) for k in ('mu', 'ss', 'kd'))
+        p_up, p_down = stats.norm.ppf(0.975), stats.norm.ppf(0.025)
+        try:
+            for lo in range(0, n_rows, batch):
+                hi = min(lo + batch, n_rows)
+                B = hi - lo
+                values_b, _ = self._values_rows(rows[lo:hi])
+                values0 = self._values_row(values_b, 0)
+                ctmpl, coffs, cfields = compile_spec_rows(kern_c.spec(values_b, d), kern_c.spec(values0, d), d, B)
+                with np.errstate(all='ignore'):
+                    loc = np.asarray(self.f_location.rows(S, values_b, B), dtype=self.dtype)
+                if prior:
+                    if need_var:
+                        dev.gp_cross_batched_fields(ctmpl, coffs, cfields, Sd, M, Xd, M, d, None, 0, None, None, None, None, kd)
+                else:
+                    tmpl, offs, fields = compile_spec_rows(self.f_kernel_noise.spec(values_b, d),
+                                                           self.f_kernel_noise.spec(values0, d), d, B)
+                    with np.errstate(all='ignore'):
+                        # the posterior's delta: tt_to_num(mapping.inv(y)) - m(X) (elliptical.py:63), non-finite entries sent
+                        # as 0, exactly as _factor / _solve('post') prepare it for one row
+                        mapped = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
+                        mapped = np.where(np.isnan(mapped), 0, np.where(np.isinf(mapped), big, mapped))
+                        delta = mapped - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype)
+                    delta = np.where(np.isfinite(delta), delta, 0).astype(self.dtype)
+                    dd = dev.upload(np.ascontiguousarray(delta))
+                    try:
+                        dev.gp_factor_batched_fields(tmpl, offs, fields, Xd, N, d, dd, K, kstride, W, a)
+                    finally:
+                        dd.free()         # a (B, N) buffer per block: not left to the garbage collector over a long chain
+                    dev.gp_cross_batched_fields(ctmpl, coffs, cfields, Sd, M, Xd, N, d, K, kstride, W, a,
+                                                mu if need_loc else None, ss if need_var else None, kd if need_var else None)
+                    if need_loc:
+                        loc = loc + dev.download(mu, B, M)                                    # elliptical.py:81-84
+                with np.errstate(all='ignore'):
+                    if need_var:
+                        dg = dev.download(kd, B, M)
+                        if noise:   # tt_to_cov acts on the whole matrix; its effect on each row's diagonal
+                            dg = np.where(np.isnan(dg), 0, np.where(np.isinf(dg), big, dg))
+                            m = dg.min(axis=1)
+                            dg = np.where(~(m > 0)[:, None], dg + (t(np.float32(1e-6)) - m)[:, None], dg)
+                        if not prior:
+                            dg = dg - dev.download(ss, B, M)
+                        dg = np.where(dg < 0, t(0), dg)                                       # tt_to_bounded(., 0) elliptical.py:94-97
+                        sd = np.sqrt(dg)
+                    for k in keys:
+                        if k in ('mean', 'median'):
+                            out[k][lo:hi] = loc
+                        elif k == 'variance':
+                            out[k][lo:hi] = dg
+                        elif k == 'std':
+                            out[k][lo:hi] = sd
+                        else:       # quantiler: mapping(location + p * kernel_sd), th_mapping scrubs its result
+                            r = loc + (p_up if k == 'quantile_up' else p_down) * sd
+                            out[k][lo:hi] = np.where(np.isnan(r), 0, np.where(np.isinf(r), big, r))
+        finally:
+            Sd.free()
+            if Xd is not Sd:
+                Xd.free()
+            if prior and kd is not None:
+                kd.free()
+        return out
 
     def dlogp_chain(self, chain, batch=None):
         """one dlogp per row of a flat-parameter chain, shape (rows, ndim) -- what fixed_dlogp averages
@@ -431,6 +551,8 @@ class GaussianProcess(EllipticalProcess):
 
 
 class WarpedGaussianProcess(GaussianProcess):
+    _CHAIN_PREDICT = False       # predict_chain takes the loop of single predictions
+
     def __init__(self, *args, **kwargs):
         if 'name' not in kwargs:
             kwargs['name'] = 'WGP'

@@ -481,6 +481,65 @@ class StochasticProcess:
         """stochastic.py:515-520: one logp per row of a flat-parameter chain"""
         return np.array([self.logp(row, array=True, prior=prior) for row in chain], dtype=np.float64)
 
+    # ---- predictions over the rows of a chain (models.py:489-519: a loop of single predictions over an MCMC trace)
+    def _chain_rows(self, chain):
+        """a 2-D array of flat parameter vectors, or anything with `.values` of that shape (a DataFrame trace)"""
+        rows = np.atleast_2d(np.asarray(getattr(chain, 'values', chain), dtype=np.float64))
+        return rows[:, :self.active.ndim]
+
+    def _predict_chain_keys(self, switches):
+        return [key for switch, key, _, _, _ in self._PREDICT_TABLE if switches.get(switch)]
+
+    def _predict_chain_loop(self, rows, space, inputs, outputs, switches, noise, prior):
+        """one `predict` per row, stacked: the route of every process without a batched form of its prediction"""
+        out = DictObj()
+        for i, row in enumerate(rows):
+            pred = self.predict(self.active.array_to_dict(row), space, inputs, outputs, prior=prior, noise=noise, **switches)
+            for k, v in pred.items():
+                v = np.asarray(v)
+                if k not in out:
+                    out[k] = np.empty((len(rows),) + v.shape, dtype=v.dtype)
+                out[k][i] = v
+        if not len(rows):
+            M = len(self.space if space is None else space)
+            for k in self._predict_chain_keys(switches):
+                out[k] = np.empty((0, M), dtype=self.dtype)
+        return out
+
+    def _chain_predict_batched(self):
+        """True when the process evaluates a block of chain rows in batched launches (GaussianProcess)"""
+        return False
+
+    def predict_chain(self, chain, space=None, inputs=None, outputs=None, mean=True, std=True, var=False, median=False,
+                      quantiles=False, noise=False, prior=False, batch=None):
+        """`predict` for every row of a flat-parameter chain: a DictObj of (rows, M) arrays under predict's keys (mean,
+        variance, std, median, quantile_up, quantile_down), row i equal to predict(array_to_dict(chain[i]), ...).  The
+        reference loops (models.py:489-519); a GaussianProcess factors and solves `batch` rows at a time in batched
+        launches (g3_gp_factor_batched_fields + g3_gp_cross_batched_fields), every other process takes the loop."""
+        rows = self._chain_rows(chain)
+        switches = dict(mean=mean, std=std, var=var, median=median, quantiles=quantiles)
+        prior = prior or not self.is_observed
+        if len(rows) and self._chain_predict_batched():
+            return self._predict_chain_blocks(rows, space, inputs, outputs, switches, noise, prior, batch)
+        return self._predict_chain_loop(rows, space, inputs, outputs, switches, noise, prior)
+
+    def average(self, chain, space=None, inputs=None, outputs=None, mean=True, std=True, var=False, median=False,
+                quantiles=False, noise=False, prior=False, batch=None, mixture=False):
+        """models.py:489-519 without its `scores`: the arithmetic mean over the rows of a chain (2-D array or anything with
+        `.values`) of every curve predict_chain returns.  mixture=True adds the moments of the equal-weight mixture of the
+        rows' predictive distributions: mixture_mean = mean of the means, mixture_variance = mean of the variances + the
+        (population) variance of the means."""
+        pred = self.predict_chain(chain, space, inputs, outputs, mean=mean or mixture, std=std, var=var or mixture,
+                                  median=median, quantiles=quantiles, noise=noise, prior=prior, batch=batch)
+        wanted = self._predict_chain_keys(dict(mean=mean, std=std, var=var, median=median, quantiles=quantiles))
+        out = DictObj()
+        for k in wanted:
+            out[k] = np.mean(pred[k], axis=0)
+        if mixture:
+            out['mixture_mean'] = np.mean(pred['mean'], axis=0)
+            out['mixture_variance'] = np.mean(pred['variance'], axis=0) + np.var(pred['mean'], axis=0)
+        return out
+
     # ---- averages over a fixed chain (stochastic.py:522-564): the rows of active.fixed_chain with
     #      the sampling dimensions overwritten by `sampling_params`
     def _fixed_rows(self, sampling_params):

@@ -403,6 +403,36 @@ int g3_gp_dlogp_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, int
                                int64_t ldx, int d, const void* L_dev, int64_t ldl, int64_t kstride, const void* invd_dev,
                                const void* a_dev, g3_dtype dt, void* Y_dev, void* Kinv_dev, void* alpha_dev, double* out_host);
 
+/* g3_gp_cross for every member of a chain, after ONE g3_gp_factor_batched(_fields) call with the same member layout
+ * (factors kstride elements apart in L_dev with leading dimension ldl, block inverses roundup(N,128)*128 apart, a_dev batch
+ * x roundup(N,128)): what the reference's average / particles loop over the rows of a trace for
+ * (g3py/bayesian/models.py:489-543).  Per member b and query point i < M, with V_b = tt_to_num(prog_b(Xs, X)) L_b^-T:
+ *     mu[b][i] = V_b[i,:] . a_b      ss[b][i] = |V_b[i,:]|^2      kdiag[b][i] = prog_b(xs_i, xs_i)
+ * mu_dev, ss_dev, kdiag_dev are batch x roundup(M,128) (entries beyond M of a row are unspecified); each may be NULL, and
+ * with mu_dev == ss_dev == NULL the factor arguments (L_dev, invd_dev, a_dev) are not looked at -- the prior needs no
+ * factorisation.  kdiag is the batched g3_gram_diag: the square-case diagonal, so NOISE / WN leaves contribute to it;
+ * to the cross block NOISE contributes nothing, as in g3_gp_cross.  V is not returned: for roundup(N,128) <= 1024 one
+ * Gram launch (member in grid.z) and one solve launch (member in grid.y) work in the context's workspace (at most 256 MB
+ * of it: longer chains take several launch pairs); larger members run the g3_gp_cross path one at a time.  Because the
+ * call comes after the factor call, a member that went through the jitter schedule or the 1e-10*I fallback is solved
+ * against the factor that was kept.  All programs share one structure; batch <= 4096.  The row sums are combined in a
+ * fixed order: two calls give the same bits.  Synchronises the context's stream once (the programs are borrowed).
+ * L_dev, invd_dev and a_dev must be what g3_gp_factor_batched(_fields) left: the solve relies on the zero strict upper
+ * triangle of every 128 x 128 block inverse and on the identity padding of the factor beyond N (rows [N, roundup(N,128))
+ * zero left of the diagonal); a buffer filled otherwise may turn its padding into NaN in valid columns. */
+int g3_gp_cross_batched(g3_ctx* ctx, const g3_kernel_prog* progs_cross_host, int batch, const void* Xs_dev, int64_t M,
+                        int64_t ldxs, const void* X_dev, int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl,
+                        int64_t kstride, const void* invd_dev, const void* a_dev, g3_dtype dt, void* mu_dev, void* ss_dev,
+                        void* kdiag_dev);
+/* The same with the members' programs given as g3_gp_factor_batched_fields takes them (template + per-member doubles at
+ * byte offsets of g3_kernel_prog; the offset of a G3_K_DOT exponent is refused); the members are expanded on the device, so
+ * a chain row costs nfield doubles of packing and PCIe.  Bit-identical to the call above on the expanded programs.  Argument numbers in negative return codes follow this signature. */
+int g3_gp_cross_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, int batch, const double* fields_host,
+                               const int32_t* offsets_host, int nfield, const void* Xs_dev, int64_t M, int64_t ldxs,
+                               const void* X_dev, int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl,
+                               int64_t kstride, const void* invd_dev, const void* a_dev, g3_dtype dt, void* mu_dev,
+                               void* ss_dev, void* kdiag_dev);
+
 /* Latent draws of the sampler (g3py/processes/gaussian.py:89-95, before the mapping):
  *     out[i][s] = loc[i] + sum_j L[i][j] Z[j][s]
  * L_dev: lower Cholesky factor of the prior / posterior covariance of the M query points, stored
