@@ -96,6 +96,8 @@ _SIGS = {
     'g3_potrf_nowait': ([_P, _P, _I64, _I64, C.c_int, _P, _P], C.c_int),
     'g3_potrf_robust': ([_P, _P, _I64, _P, _I64, _I64, C.c_int, C.c_int, C.POINTER(C.c_int),
                          C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
+    'g3_potrf_robust_batched': ([_P, _P, _I64, _I64, _P, _I64, _I64, C.c_int, _I64, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                 C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
     'g3_trsm_rlt': ([_P, _P, _I64, _I64, _P, _I64, _I64, C.c_int, _P], C.c_int),
     'g3_trtri_full': ([_P, _P, _I64, _P, _P, _P, _P, C.c_int], C.c_int),
     'g3_trsm_full': ([_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, C.c_int], C.c_int),
@@ -117,6 +119,12 @@ _SIGS = {
                              _P, _P, C.c_int, _P, _P, _P], C.c_int),
     'g3_gp_cross_batched_fields': ([_P, C.POINTER(KernelProg), C.c_int, _P, _P, C.c_int, _P, _I64, _I64, _P, _I64, _I64,
                                     C.c_int, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P], C.c_int),
+    'g3_gp_draws_batched': ([_P, C.POINTER(KernelProg), C.c_int, _P, _I64, _I64, _P, _I64, _I64, C.c_int, _P, _I64, _I64,
+                             _P, _P, C.c_int, C.c_int, _P, _P, _I64, _P, _P, _P, C.c_int, C.POINTER(C.c_int),
+                             C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
+    'g3_gp_draws_batched_fields': ([_P, C.POINTER(KernelProg), C.c_int, _P, _P, C.c_int, _P, _I64, _I64, _P, _I64, _I64,
+                                    C.c_int, _P, _I64, _I64, _P, _P, C.c_int, C.c_int, _P, _P, _I64, _P, _P, _P, C.c_int,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
     'g3_gp_sample': ([_P, _P, _I64, _I64, _P, _P, _I64, C.c_int, _P], C.c_int),
     'g3_grad_layout': ([C.POINTER(KernelProg), C.POINTER(GradMap)], C.c_int),
     'g3_potri': ([_P, _P, _I64, _I64, _P, C.c_int, _P, _I64, _P, _I64], C.c_int),

@@ -374,31 +374,6 @@ extern "C" int g3_copy2d(g3_ctx* ctx, void* dst, int64_t ldd, const void* src, i
 }
 
 // ----------------------------------------------------------------------------- small kernels
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_min(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    T u = __shfl_down(v, o, 64);
-    v = (u < v || u != u) ? u : v;  // NaN propagates like numpy.min
-  }
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    T u = __shfl_down(v, o, 64);
-    v = (u > v || u != u) ? u : v;
-  }
-  return v;
-}
-
 // one workgroup (1024 threads): out = [min, mean, max] of diag(A); optionally applies
 // tt_to_cov's lift  A_ii += (1e-6f - min) when min <= 0  (tensors.py:95-98)
 template <typename T>
@@ -1404,6 +1379,238 @@ extern "C" int g3_gp_cross_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmp
   return (rc <= -4 && rc >= -19) ? rc - 3 : rc;
 }
 
+
+// ---------------------------------------------------------------------------------------
+// One joint draw of the curve per chain member after ONE g3_gp_factor_batched sweep (models.py:521-543: `particles`, a
+// loop of single sampler calls in the reference -> gaussian.py:89-97, elliptical.py:86-92 per row).  Per launch group:
+//   Ks_b -> V_b        one rectangular Gram launch, one solve launch that keeps V (g3_crossb.hip), mu_b on the way
+//   C_b = P_b - V_b V_b^T   one square Gram launch (scrubbed and lifted per member with the noise kernel, as
+//                      _prior_gram / tt_to_cov do), then the lower triangle through the batched MFMA GEMM of the
+//                      factorisation sweep (member in grid.y; V and C have different strides: V plays the part of the
+//                      block-inverse region of ctx->batch mode)
+//   Lp_b               the device-side jitter schedule (g3_drawsb.hip), or the single call per member beyond 256 rows
+//   out_b              loc_b + mu_b + Lp_b Z_b, one launch
+// Everything lives in the context's workspace, G3_CROSSB_WORK bytes of it at most per group.
+static int gp_draws_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, const void* Xs, int64_t M, int64_t ldxs,
+                                 const void* X, int64_t N, int64_t ldx, int d, const void* L, int64_t ldl, int64_t kstride,
+                                 const void* invd, const void* a, g3_dtype dt, int lift, const void* loc, const void* Z, int64_t S,
+                                 void* out, void* C_out, void* Lp_out, int maxtries, int* tries_host, int* fallback_host,
+                                 double* jitter_host) {
+  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
+  if (!Xs) return -4;
+  if (M <= 0) return -5;
+  if (d < 1 || d > G3_MAXCOLS) return -10;
+  if (ldxs < d) return -6;
+  if (dt != G3_F64 && dt != G3_F32) return -16;
+  const bool post = L != nullptr;
+  const int64_t Np = post ? g3_roundup(N, G3_LB) : 0, Mp = g3_roundup(M, 128);
+  const size_t es = g3_esize(dt);
+  const int64_t al = 16 / (int64_t)es;
+  if (post) {
+    if (!X) return -7;
+    if (N <= 0) return -8;
+    if (ldx < d) return -9;
+    if (ldl < Np || ldl % al) return -12;
+    if (kstride < Np * ldl || kstride % al) return -13;
+    if (!invd) return -14;
+    if (!a) return -15;
+  }
+  if (!loc) return -18;
+  if (!Z) return -19;
+  if (S <= 0) return -20;
+  if (!out) return -21;
+  if (maxtries < 0) return -24;
+  g3_kernel_prog first;
+  mp.member(0, &first);
+  if (mp.progs) {
+    for (int b = 0; b < batch; ++b)
+      if (g3i_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return -2;
+  } else if (g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(&first, d)) {
+    return -2;
+  }
+  // device copies of the members' programs, as g3_gp_cross_batched makes them
+  const size_t pbytes = (size_t)batch * sizeof(g3_kernel_prog);
+  const size_t fbytes = mp.progs ? 0 : (size_t)batch * mp.nfield * sizeof(double);
+  const size_t obytes = mp.progs ? 0 : (((size_t)mp.nfield * sizeof(int32_t) + 15) & ~(size_t)15);
+  const size_t head = (pbytes + (mp.progs ? 0 : sizeof(g3_kernel_prog)) + fbytes + obytes + 255) & ~(size_t)255;
+  int rc = ensure_bbuf(ctx, head);
+  if (rc) return rc;
+  g3_kernel_prog* dprogs = (g3_kernel_prog*)ctx->bbuf;
+  if (mp.progs) {
+    G3_HIP(hipMemcpyAsync(dprogs, mp.progs, pbytes, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    g3_kernel_prog* dtmpl = (g3_kernel_prog*)((char*)dprogs + pbytes);
+    double* dfields = (double*)(dtmpl + 1);
+    int32_t* doffs = (int32_t*)((char*)dfields + fbytes);
+    G3_HIP(hipMemcpyAsync(dtmpl, mp.tmpl, sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
+    if (mp.nfield) {
+      G3_HIP(hipMemcpyAsync(dfields, mp.fields, fbytes, hipMemcpyHostToDevice, ctx->stream));
+      G3_HIP(hipMemcpyAsync(doffs, mp.offs, (size_t)mp.nfield * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    hipLaunchKernelGGL(expand_progs_kernel, dim3(batch), dim3(256), 0, ctx->stream, dprogs, dtmpl, dfields, doffs, mp.nfield);
+    G3_LAUNCH_CHECK();
+  }
+  G3_HIP(hipStreamSynchronize(ctx->stream));          // the host arrays are borrowed for the call only
+  // the workspace of one launch group of cb members: [scratch of the single robust call] V C Lp mu loc Z out res [inverses]
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const bool fused = Mp <= 2 * G3_LB;                 // the device-side schedule; larger members: g3_potrf_robust one by one
+  const bool big = post && Np > 1024;                 // beyond the one-launch solve: g3_gp_cross's path per member
+  const size_t v1 = post ? (size_t)Mp * Np * es : 0, c1 = (size_t)Mp * Mp * es, m1 = (size_t)Mp * es, l1 = (size_t)M * es,
+               z1 = (size_t)M * S * es, r1 = 3 * sizeof(double);
+  const size_t per = v1 + (C_out ? 0 : c1) + (Lp_out ? 0 : c1) + m1 + l1 + 2 * z1 + r1;
+  // the parts that do not grow with the group count against the cap too: the single robust call's copy, or the fused kernel's
+  // scratch for the block inverses (one slot per workgroup, at most the group's size)
+  const size_t fixed = (fused ? up(g3i_robust_scratch_bytes(batch, M, dt)) : up(c1)) + 9 * 256;      // + the regions' alignment
+  int64_t cb = G3_CROSSB_WORK > fixed ? (int64_t)((G3_CROSSB_WORK - fixed) / per) : 0;
+  cb = cb < 1 ? 1 : (cb > batch ? batch : cb);
+  const size_t o_scr = 0, o_v = o_scr + (fused ? 0 : up(c1)), o_c = o_v + up(cb * v1), o_l = o_c + (C_out ? 0 : up(cb * c1)),
+               o_mu = o_l + (Lp_out ? 0 : up(cb * c1)), o_loc = o_mu + up(cb * m1), o_z = o_loc + up(cb * l1),
+               o_out = o_z + up(cb * z1), o_res = o_out + up(cb * z1), o_w = o_res + up(cb * r1),
+               total = o_w + (fused ? up(g3i_robust_scratch_bytes((int)cb, M, dt)) : 0);
+  rc = g3i_ensure_work(ctx, total);
+  if (rc) return rc;
+  char* wk = (char*)ctx->work;
+  const int64_t wstride = Np * G3_LB;
+  double* hres = (double*)malloc((size_t)cb * r1);
+  if (!hres) return G3_ERR_NOMEM;
+  for (int64_t b0 = 0; b0 < batch && !rc; b0 += cb) {
+    const int nb = (int)(batch - b0 < cb ? batch - b0 : cb);
+    char* V = wk + o_v;
+    char* Cb = C_out ? (char*)C_out + (size_t)b0 * c1 : wk + o_c;
+    char* Lp = Lp_out ? (char*)Lp_out + (size_t)b0 * c1 : wk + o_l;
+    char* mu = post ? wk + o_mu : nullptr;
+    const g3_kernel_prog* dp = dprogs + b0;
+    g3_kernel_prog mine;
+    mp.member((int)b0, &mine);
+    if (hipMemcpyAsync(wk + o_loc, (const char*)loc + (size_t)b0 * l1, (size_t)nb * l1, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(wk + o_z, (const char*)Z + (size_t)b0 * z1, (size_t)nb * z1, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+      snprintf(ctx->err, sizeof(ctx->err), "g3_gp_draws_batched: upload of loc / Z failed");
+      rc = G3_ERR_HIP;
+      break;
+    }
+    if (post && !big) {
+      int pr = g3i_prof_begin(ctx, G3_TAG_CROSS_GRAM, (double)nb * ((double)(N + M) * d + (double)N * M) * es);
+      rc = g3i_gram_rect_batched(ctx, dp, &mine, nb, Xs, M, ldxs, X, N, ldx, d, dt, V, Np, Mp * Np, Mp, Np, G3_GRAM_SCRUB, 0);
+      g3i_prof_end(ctx, pr);
+      if (rc) break;
+      pr = g3i_prof_begin(ctx, G3_TAG_TRSM, (double)nb * (double)N * N * M);
+      rc = g3i_cross_solve_batched(ctx, V, Mp * Np, (const char*)L + (size_t)b0 * kstride * es, ldl, kstride,
+                                   (const char*)invd + (size_t)b0 * wstride * es, wstride, (const char*)a + (size_t)b0 * Np * es, Np,
+                                   mu, nullptr, Mp, Mp, N, Np, nb, dt, 1);
+      g3i_prof_end(ctx, pr);
+      if (rc) break;
+    } else if (post) {
+      for (int b = 0; b < nb && !rc; ++b) {
+        g3_kernel_prog pb;
+        mp.member((int)b0 + b, &pb);
+        char* Vb = V + (size_t)b * v1;
+        rc = g3_gram(ctx, &pb, Xs, M, ldxs, X, N, ldx, d, dt, Vb, Np, Mp, Np, G3_GRAM_SCRUB);
+        if (!rc) rc = g3i_reset_info(ctx);
+        if (!rc) rc = g3i_trsm_rlt(ctx, (const char*)L + (size_t)(b0 + b) * kstride * es, Np, ldl, Vb, Mp, Np, dt,
+                                   (const char*)invd + (size_t)(b0 + b) * wstride * es);
+        if (!rc) rc = rows_dot_ss_launch(ctx, Vb, M, N, Np, (const char*)a + (size_t)(b0 + b) * Np * es, dt, mu + (size_t)b * m1, nullptr);
+      }
+      if (rc) break;
+    }
+    // P_b = prog_b(Xs, Xs); with the noise kernel tt_to_cov: scrubbed, non-positive diagonal lifted (elliptical.py:70,74)
+    int pr = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)nb * ((double)M * d + 0.5 * (double)M * (M + 1)) * es);
+    rc = g3i_gram_batched(ctx, dp, &mine, nb, Xs, M, ldxs, d, dt, Cb, Mp, Mp * Mp, Mp, G3_GRAM_LOWER | (lift ? G3_GRAM_SCRUB : 0u));
+    if (!rc && lift) {
+      if (dt == G3_F64)
+        hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(nb), dim3(1024), 0, ctx->stream, (double*)Cb, M, Mp, (double*)nullptr, 1, Mp * Mp);
+      else
+        hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(nb), dim3(1024), 0, ctx->stream, (float*)Cb, M, Mp, (double*)nullptr, 1, Mp * Mp);
+    }
+    g3i_prof_end(ctx, pr);
+    if (rc) break;
+    if (hipGetLastError() != hipSuccess) { rc = G3_ERR_HIP; break; }
+    if (post) {
+      ctx->batch = nb;                      // (set first: the flags of all nb members are cleared)
+      rc = g3i_reset_info(ctx);
+      if (rc) { ctx->batch = 0; break; }
+      ctx->bstride = Mp * Mp;
+      ctx->bstride_w = Mp * Np;
+      ctx->bw_base = V;
+      ctx->bw_bytes = (size_t)nb * v1;
+      rc = g3i_gemm_nt(ctx, Cb, Mp, V, Np, V, Np, Mp, Mp, Np, -1.0, 1.0, dt, 1);          // lower(C_b) -= V_b V_b^T  (elliptical.py:86-91)
+      ctx->batch = 0;
+      ctx->bw_base = nullptr;
+      if (rc) break;
+    }
+    int* tr = tries_host ? tries_host + b0 : nullptr;
+    int* fb = fallback_host ? fallback_host + b0 : nullptr;
+    double* jt = jitter_host ? jitter_host + b0 : nullptr;
+    if (fused) {
+      pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)nb * (double)M * M * M / 3.0);
+      rc = g3i_potrf_robust_batched(ctx, Cb, Mp, Mp * Mp, Lp, Mp, Mp * Mp, nb, M, dt, maxtries, wk + o_w, (double*)(wk + o_res));
+      g3i_prof_end(ctx, pr);
+      if (rc) break;
+    } else {
+      // the single call works in the first bytes of the context's workspace: o_scr keeps them free for it
+      if (hipMemsetAsync(Lp, 0, (size_t)nb * c1, ctx->stream) != hipSuccess) { rc = G3_ERR_HIP; break; }
+      for (int b = 0; b < nb && !rc; ++b)
+        rc = g3_potrf_robust(ctx, Cb + (size_t)b * c1, Mp, Lp + (size_t)b * c1, Mp, M, dt, maxtries, tr ? tr + b : nullptr,
+                             fb ? fb + b : nullptr, jt ? jt + b : nullptr);
+      if (rc) break;
+    }
+    rc = g3i_draws_batched(ctx, Lp, Mp, Mp * Mp, wk + o_loc, mu, Mp, wk + o_z, wk + o_out, M, S, nb, dt);
+    if (rc) break;
+    hipError_t e = hipMemcpyAsync((char*)out + (size_t)b0 * z1, wk + o_out, (size_t)nb * z1, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && fused) e = hipMemcpyAsync(hres, wk + o_res, (size_t)nb * r1, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      snprintf(ctx->err, sizeof(ctx->err), "g3_gp_draws_batched: download failed: %s", hipGetErrorString(e));
+      rc = G3_ERR_HIP;
+      break;
+    }
+    if (fused)
+      for (int b = 0; b < nb; ++b) {
+        if (tr) tr[b] = (int)hres[3 * b];
+        if (fb) fb[b] = (int)hres[3 * b + 1];
+        if (jt) jt[b] = hres[3 * b + 2];
+      }
+  }
+  free(hres);
+  return rc;
+}
+
+extern "C" int g3_gp_draws_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const void* Xs, int64_t M, int64_t ldxs,
+                                   const void* X, int64_t N, int64_t ldx, int d, const void* L, int64_t ldl, int64_t kstride,
+                                   const void* invd, const void* a, g3_dtype dt, int lift, const void* loc, const void* Z, int64_t S,
+                                   void* out, void* C_dev, void* Lp_dev, int maxtries, int* tries_host, int* fallback_host,
+                                   double* jitter_host) {
+  if (!ctx) return -1;
+  g3_dev_guard _dg(ctx);
+  if (!progs) return -2;
+  MemberProgs mp;
+  mp.progs = progs;
+  return gp_draws_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, lift, loc, Z, S, out, C_dev,
+                               Lp_dev, maxtries, tries_host, fallback_host, jitter_host);
+}
+
+extern "C" int g3_gp_draws_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl, int batch, const double* fields,
+                                          const int32_t* offsets, int nfield, const void* Xs, int64_t M, int64_t ldxs,
+                                          const void* X, int64_t N, int64_t ldx, int d, const void* L, int64_t ldl,
+                                          int64_t kstride, const void* invd, const void* a, g3_dtype dt, int lift, const void* loc,
+                                          const void* Z, int64_t S, void* out, void* C_dev, void* Lp_dev, int maxtries,
+                                          int* tries_host, int* fallback_host, double* jitter_host) {
+  if (!ctx) return -1;
+  g3_dev_guard _dg(ctx);
+  if (!tmpl) return -2;
+  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
+  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
+  if (nfield && (!fields || !offsets)) return -4;
+  for (int i = 0; i < nfield; ++i)
+    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
+  MemberProgs mp;
+  mp.tmpl = tmpl;
+  mp.fields = fields;
+  mp.offs = offsets;
+  mp.nfield = nfield;
+  const int rc = gp_draws_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, lift, loc, Z, S, out,
+                                       C_dev, Lp_dev, maxtries, tries_host, fallback_host, jitter_host);
+  return (rc <= -4 && rc >= -24) ? rc - 3 : rc;
+}
 
 // draws = loc + L Z  (gaussian.py:92-95).  Z^T and the product live in the context's workspace.
 template <typename T>

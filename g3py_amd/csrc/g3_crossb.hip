@@ -14,7 +14,8 @@
 // (rows of L, rows of W) is different for every wave, so it goes from global memory (L2: the member's factor is re-read by
 // every stripe) straight into registers, one 16-byte chunk of consecutive reduction indices per lane -- the reduction
 // index may be visited in any order as long as A and B agree (g3_gemm.hip).
-// Np <= 256: the stripe's V never leaves LDS (32 x (Np + pad): 66 KB for fp64 at Np = 256, two workgroups per CU).
+// Np <= 256: the stripe's V never leaves LDS (32 x (Np + pad): 66 KB for fp64 at Np = 256, two workgroups per CU) -- unless
+// the caller wants it (KEEPV): then every block of V is also stored over the block of Ks it came from.
 // 256 < Np <= 1024: V[:, k] overwrites Ks[:, k] -- the stripe of the cross-Gram workspace this workgroup owns and has just
 // consumed -- and the update product reads it back from there (L2); T alone is staged in LDS.
 // What the kernel relies on (a wave reduces over t < 32 (w + 1), more than t <= c, and padding takes part in the products, so
@@ -30,7 +31,7 @@
 #define CB_BM 32          // rows of a stripe
 #define CB_PAD_BYTES 64   // row pitch = columns * size + 64 B: the 64 lanes' 16-byte chunks (16 rows x 4 chunks) hit distinct banks
 
-template <typename T, bool SPILL>
+template <typename T, bool SPILL, bool KEEPV>
 __global__ void __launch_bounds__(256, 2)
 cross_solve_kernel(T* Ks, int64_t sstride, const T* L, int64_t ldl, int64_t lstride, const T* W, int64_t wstride, const T* a,
                    int64_t astride, T* mu, T* ss, int64_t ostride, int N, int Np) {
@@ -121,7 +122,7 @@ cross_solve_kernel(T* Ks, int64_t sstride, const T* L, int64_t ldl, int64_t lstr
     }
     __syncthreads();          // every wave has read T: its place may be overwritten
     // ---- keep V[:, k] for the later blocks, and its share of the row sums (columns beyond N are padding)
-    const bool keep = k + 1 < nblk;
+    const bool keep = KEEPV || k + 1 < nblk;
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       const int col = 32 * w + 16 * ct + r16;
@@ -134,8 +135,8 @@ cross_solve_kernel(T* Ks, int64_t sstride, const T* L, int64_t ldl, int64_t lstr
           const T v = acc[rt][ct][r];
           const int row = 16 * rt + MF::row(lane, r);
           if (keep) {
-            if (SPILL) Ks[(int64_t)row * Np + c0 + col] = v;
-            else Vs[row * P + c0 + col] = v;
+            if (SPILL || KEEPV) Ks[(int64_t)row * Np + c0 + col] = v;
+            if (!SPILL) Vs[row * P + c0 + col] = v;
           }
           if (in) {
             pm[rt][r] += (double)v * av;
@@ -175,13 +176,13 @@ cross_solve_kernel(T* Ks, int64_t sstride, const T* L, int64_t ldl, int64_t lstr
   }
 }
 
-template <typename T, bool SPILL>
+template <typename T, bool SPILL, bool KEEPV>
 static int cross_solve_launch(g3_ctx* ctx, T* Ks, int64_t sstride, const T* L, int64_t ldl, int64_t lstride, const T* W,
                               int64_t wstride, const T* a, int64_t astride, T* mu, T* ss, int64_t ostride, int64_t Mp, int64_t N,
                               int64_t Np, int batch) {
   const size_t P = (size_t)(SPILL ? G3_LB : Np) + CB_PAD_BYTES / sizeof(T);
   const size_t lds = (size_t)CB_BM * P * sizeof(T) + (size_t)4 * CB_BM * 2 * sizeof(double);
-  auto kern = cross_solve_kernel<T, SPILL>;
+  auto kern = cross_solve_kernel<T, SPILL, KEEPV>;
   static bool attr_set[G3_MAX_DEVICES] = {};
   const int dev_slot = ctx->device & (G3_MAX_DEVICES - 1);
   if (!attr_set[dev_slot]) {
@@ -194,19 +195,22 @@ static int cross_solve_launch(g3_ctx* ctx, T* Ks, int64_t sstride, const T* L, i
   return G3_OK;
 }
 
-// Ks: batch x Mp x Np (compact, members sstride apart), consumed (SPILL: overwritten by V).  L / W / a as g3_gp_factor_batched
+// Ks: batch x Mp x Np (compact, members sstride apart), consumed (SPILL: overwritten by V; keepv: V_b is left in it whole,
+// for the posterior covariance of g3_gp_draws_batched -- the sums mu / ss are formed exactly as without it).  L / W / a as g3_gp_factor_batched
 // leaves them.  mu, ss (either may be null): batch x ostride.  Np a multiple of 128, <= 1024; Mp a multiple of 128.
 int g3i_cross_solve_batched(g3_ctx* ctx, void* Ks, int64_t sstride, const void* L, int64_t ldl, int64_t lstride, const void* W,
                             int64_t wstride, const void* a, int64_t astride, void* mu, void* ss, int64_t ostride, int64_t Mp,
-                            int64_t N, int64_t Np, int batch, g3_dtype dt) {
+                            int64_t N, int64_t Np, int batch, g3_dtype dt, int keepv) {
   if (Np % G3_LB || Np > 1024 || Mp % CB_BM || batch < 1 || N > Np) {
     snprintf(ctx->err, sizeof(ctx->err), "batched cross solve: shape not covered (Np=%lld Mp=%lld)", (long long)Np, (long long)Mp);
     return G3_ERR_HIP;
   }
   const bool spill = Np > 2 * G3_LB;
 #define G3_CB_LAUNCH(TT, SP)                                                                                                  \
-  return cross_solve_launch<TT, SP>(ctx, (TT*)Ks, sstride, (const TT*)L, ldl, lstride, (const TT*)W, wstride, (const TT*)a,   \
-                                    astride, (TT*)mu, (TT*)ss, ostride, Mp, N, Np, batch)
+  return keepv ? cross_solve_launch<TT, SP, true>(ctx, (TT*)Ks, sstride, (const TT*)L, ldl, lstride, (const TT*)W, wstride,   \
+                                                  (const TT*)a, astride, (TT*)mu, (TT*)ss, ostride, Mp, N, Np, batch)         \
+               : cross_solve_launch<TT, SP, false>(ctx, (TT*)Ks, sstride, (const TT*)L, ldl, lstride, (const TT*)W, wstride,  \
+                                                   (const TT*)a, astride, (TT*)mu, (TT*)ss, ostride, Mp, N, Np, batch)
   if (dt == G3_F64) {
     if (spill) G3_CB_LAUNCH(double, true);
     G3_CB_LAUNCH(double, false);

@@ -406,16 +406,27 @@ static inline void g3h_stair_chunks(const std::vector<int64_t>& seg_rows, const 
 
 // ---- CholeskyRobust's jitter schedule (g3py/libs/tensors.py:203-213): dK = mean(diag) * 1e-6 (float32 constants, as
 // the reference's Theano graph has them), non-positive diagonals lifted by mean * 1e-6 - min, then up to 20 retries
-// with dK *= 10.  One definition for the single-GPU, batched and multi-GPU callers.
+// with dK *= 10.  One definition for the single-GPU, batched and multi-GPU callers -- and for the kernel that runs the
+// schedule per member on the device (g3_drawsb.hip): the qualifier exists only under hipcc, this header is also host C++.
+#if defined(__HIPCC__)
+#define G3H_HD __host__ __device__
+#else
+#define G3H_HD
+#endif
 struct G3hJitter {
   double dK, lift;
   int tries;
-  G3hJitter(double diag_mean, double diag_min) : dK(diag_mean * (double)1e-6f), lift(0.0), tries(0) {
+  G3H_HD G3hJitter(double diag_mean, double diag_min) : dK(diag_mean * (double)1e-6f), lift(0.0), tries(0) {
     if (diag_min <= 0.0) lift = diag_mean * (double)1e-6f - diag_min;
   }
-  double value() const { return lift + dK; }        // what is added to the diagonal in this attempt
-  bool usable() const { const double v = lift + dK; return v == v; }   // NaN statistics: every retry fails
-  void next() { dK *= (double)10.0f; ++tries; }
+  G3H_HD double value() const { return lift + dK; }        // what is added to the diagonal in this attempt
+  G3H_HD bool usable() const { const double v = lift + dK; return v == v; }   // NaN statistics: every retry fails
+  G3H_HD void next() { dK *= (double)10.0f; ++tries; }
+  // sp.linalg.cholesky(check_finite=True) raises on NaN / Inf input, so every retry fails: `nonfinite` entries in the lower
+  // triangle, or a diagonal mean that is not a finite number
+  G3H_HD static bool input_finite(double nonfinite, double diag_mean) {
+    return nonfinite == 0.0 && diag_mean == diag_mean && (diag_mean < 0 ? -diag_mean : diag_mean) <= 1.7976931348623157e308;
+  }
   static int max_tries() { return 20; }
 };
 

@@ -144,6 +144,32 @@ static inline bool g3_on_bulk_stream(const g3_ctx* ctx) {
 static inline size_t g3_esize(g3_dtype dt) { return dt == G3_F64 ? 8 : 4; }
 static inline int64_t g3_roundup(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
 
+// wave reductions in a fixed order (lane 0 holds the result); min / max propagate NaN like numpy
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    T u = __shfl_down(v, o, 64);
+    v = (u < v || u != u) ? u : v;  // NaN propagates like numpy.min
+  }
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    T u = __shfl_down(v, o, 64);
+    v = (u > v || u != u) ? u : v;
+  }
+  return v;
+}
+
 // a context on the caller's stream that creates no stream of its own; the low-priority side stream on first need
 int g3i_ctx_create_on(int device, hipStream_t stream, g3_ctx** out);
 int g3i_ensure_side_stream(g3_ctx* ctx);
@@ -232,7 +258,15 @@ int g3i_gram_diag_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, int batch, 
 // batched posterior cross solve (g3_crossb.hip): Ks = batch x Mp x Np cross-Gram blocks (consumed), mu / ss batch x ostride
 int g3i_cross_solve_batched(g3_ctx* ctx, void* Ks, int64_t sstride, const void* L, int64_t ldl, int64_t lstride, const void* W,
                             int64_t wstride, const void* a, int64_t astride, void* mu, void* ss, int64_t ostride, int64_t Mp,
-                            int64_t N, int64_t Np, int batch, g3_dtype dt);
+                            int64_t N, int64_t Np, int batch, g3_dtype dt, int keepv = 0);
+// CholeskyRobust for `batch` matrices of n <= 256 rows with the jitter schedule on the device (g3_drawsb.hip): one launch, no
+// host round trip; wscr = g3i_robust_scratch_bytes of device memory, res_dev = batch x [tries, fallback, jitter] doubles
+size_t g3i_robust_scratch_bytes(int batch, int64_t n, g3_dtype dt);
+int g3i_potrf_robust_batched(g3_ctx* ctx, const void* K, int64_t ldk, int64_t kstride, void* L, int64_t ldl, int64_t lstride, int batch,
+                             int64_t n, g3_dtype dt, int maxtries, void* wscr, double* res_dev);
+// out[b] = loc[b] (+ mu[b]) + Lp_b Z[b]: Lp factors lstride apart, loc batch x M, mu batch x mustride or null, Z / out batch x M x S
+int g3i_draws_batched(g3_ctx* ctx, const void* Lp, int64_t ldl, int64_t lstride, const void* loc, const void* mu, int64_t mustride,
+                      const void* Z, void* out, int64_t M, int64_t S, int batch, g3_dtype dt);
 int g3i_validate_prog(const g3_kernel_prog* p, int d);
 // the Gram kernel generated for prog's structure (g3_gram_jit.hip); 0 = launched, 1 = none (the caller interprets)
 int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_prog* prog_dev, int batch, const void* X1, int64_t n1,

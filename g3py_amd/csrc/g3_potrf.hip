@@ -895,8 +895,7 @@ static int robust_t(g3_ctx* ctx, const T* K, int64_t ldk, T* L, int64_t ldl, int
     G3_LAUNCH_CHECK();
     G3_HIP(hipMemcpyAsync(ctx->h_stats, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     G3_HIP(hipStreamSynchronize(ctx->stream));
-    const bool finite = (*(unsigned long long*)ctx->h_stats == 0) && (st[1] == st[1]) &&
-                        (fabs(st[1]) <= 1.7976931348623157e308);
+    const bool finite = G3hJitter::input_finite((double)*(unsigned long long*)ctx->h_stats, st[1]);
     bool ok = false;
     for (int t = 0; t < maxtries; ++t) {
       ++tries;

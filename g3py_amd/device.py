@@ -257,6 +257,19 @@ class Device:
         _check(self, rc, 'g3_potrf_robust')
         return tries.value, bool(fb.value), jit.value
 
+    def potrf_robust_batched(self, K, kstride, L, lstride, batch, n, maxtries=20):
+        """potrf_robust for `batch` n x n matrices `kstride` elements apart in K, factors `lstride` apart in L (each lower
+        and zero elsewhere within its roundup(n, 128)-square slot); n <= 256 runs the jitter schedule on the device, one
+        launch for the batch.  Returns (tries, fallback, jitter) arrays of length batch."""
+        B = int(batch)
+        tries, fb, jit = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float64)
+        rc = self.lib.g3_potrf_robust_batched(self.ctx, K.ptr, K.ld, int(kstride), L.ptr, L.ld, int(lstride), B, n,
+                                              _lib.dtype_code(K.dtype), maxtries, tries.ctypes.data_as(C.POINTER(C.c_int)),
+                                              fb.ctypes.data_as(C.POINTER(C.c_int)),
+                                              jit.ctypes.data_as(C.POINTER(C.c_double)))
+        _check(self, rc, 'g3_potrf_robust_batched')
+        return tries, fb.astype(bool), jit
+
     def trsm_rlt(self, L, n, B, m, have_inverses=False):
         rc = self.lib.g3_trsm_rlt(self.ctx, L.ptr, n, L.ld, B.ptr, m, B.ld, _lib.dtype_code(L.dtype), None)
         _check(self, rc, 'g3_trsm_rlt')
@@ -368,6 +381,50 @@ class Device:
                                                  K.ld if K is not None else 0, kstride, self._ptr(W), self._ptr(a),
                                                  _lib.dtype_code(out.dtype), self._ptr(mu), self._ptr(ss), self._ptr(kdiag))
         _check(self, rc, 'g3_gp_cross_batched_fields')
+
+    def _draws_args(self, Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm, Lp, maxtries):
+        dtype = Xs.dtype
+        Z = np.ascontiguousarray(Z, dtype=dtype)
+        loc = np.ascontiguousarray(loc, dtype=dtype)
+        if Z.ndim != 3 or Z.shape[1] != M or loc.shape != (Z.shape[0], M):
+            raise G3Error('gp_draws_batched: loc must be (B, M) and Z (B, M, S)')
+        B, _, S = Z.shape
+        out = np.empty((B, M, S), dtype=dtype)
+        tries, fb, jit = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float64)
+        args = (Xs.ptr, M, Xs.ld, self._ptr(X), N, X.ld if X is not None else 0, d, self._ptr(K),
+                K.ld if K is not None else 0, int(kstride), self._ptr(W), self._ptr(a), _lib.dtype_code(dtype), int(bool(lift)),
+                loc.ctypes.data, Z.ctypes.data, S, out.ctypes.data, self._ptr(Cm), self._ptr(Lp), int(maxtries),
+                tries.ctypes.data_as(C.POINTER(C.c_int)), fb.ctypes.data_as(C.POINTER(C.c_int)),
+                jit.ctypes.data_as(C.POINTER(C.c_double)))
+        return B, args, (out, tries, fb, jit), (loc, Z)      # the last: only keeps the converted host arrays alive over the call
+
+    def gp_draws_batched(self, progs, Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm=None, Lp=None, maxtries=20):
+        """after gp_factor_batched on the same buffers: per member b one set of joint draws loc[b] + mu_b + Lp_b Z[b] with
+        Lp_b = cholesky_robust(K_b(Xs, Xs) - V_b V_b^T) (lift: the noise kernel's tt_to_cov on K_b(Xs, Xs)).  loc (B, M) and
+        Z (B, M, S) are host arrays; Cm / Lp: optional device (B * Mp, Mp) buffers for the covariances and factors.  With
+        K None the draws come from the prior.  Returns (out (B, M, S), tries, fallback, jitter)."""
+        arr = progs if isinstance(progs, C.Array) else (_lib.KernelProg * len(progs))(*progs)
+        B, args, res, keep = self._draws_args(Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm, Lp, maxtries)
+        if len(arr) != B:
+            raise G3Error('gp_draws_batched: %d programs for %d members' % (len(arr), B))
+        _check(self, self.lib.g3_gp_draws_batched(self.ctx, arr, B, *args), 'g3_gp_draws_batched')
+        return res[0], res[1], res[2].astype(bool), res[3]
+
+    def gp_draws_batched_fields(self, tmpl, offsets, fields, Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm=None, Lp=None,
+                                maxtries=20):
+        """gp_draws_batched for members given as template + fields (see compile_spec_rows), after
+        gp_factor_batched_fields on the same buffers"""
+        fields = np.ascontiguousarray(fields, dtype=np.float64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        nf = fields.shape[1]
+        if len(offsets) != nf:
+            raise G3Error('gp_draws_batched_fields: %d offsets for %d fields' % (len(offsets), nf))
+        B, args, res, keep = self._draws_args(Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm, Lp, maxtries)
+        if fields.shape[0] != B:
+            raise G3Error('gp_draws_batched_fields: %d field rows for %d members' % (fields.shape[0], B))
+        rc = self.lib.g3_gp_draws_batched_fields(self.ctx, C.byref(tmpl), B, fields.ctypes.data, offsets.ctypes.data, nf, *args)
+        _check(self, rc, 'g3_gp_draws_batched_fields')
+        return res[0], res[1], res[2].astype(bool), res[3]
 
     def gp_dlogp_batched(self, progs, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha):
         """after gp_factor_batched: per member K^-1, alpha and the kernel-parameter sums; returns (B, nslots)"""

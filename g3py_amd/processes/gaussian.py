@@ -230,6 +230,37 @@ class GaussianProcess(EllipticalProcess):
         from .hypers.mappings import Identity
         return bool(type(self)._CHAIN_PREDICT and self._dist is None and type(self.f_mapping) is Identity)
 
+    def _chain_block_members(self, rows_b, kern, S, X, y, prior):
+        """what one block of chain rows hands the batched entry points: the rows' values, the members of `kern` (the
+        cross / prior kernel) as template + fields, the rows' location at the query points S and -- a posteriori -- the
+        members of the observation kernel with the rows' delta = tt_to_num(mapping.inv(y)) - m(X) (elliptical.py:63),
+        non-finite entries sent as 0, exactly as _factor / _solve('post') prepare it for one row"""
+        B, d = len(rows_b), S.shape[1]
+        big = self.dtype.type(np.float32(1e10))
+        values_b, _ = self._values_rows(rows_b)
+        values0 = self._values_row(values_b, 0)
+        members = compile_spec_rows(kern.spec(values_b, d), kern.spec(values0, d), d, B)
+        with np.errstate(all='ignore'):
+            loc = np.asarray(self.f_location.rows(S, values_b, B), dtype=self.dtype)
+        if prior:
+            return values_b, members, loc, None, None
+        obs = compile_spec_rows(self.f_kernel_noise.spec(values_b, d), self.f_kernel_noise.spec(values0, d), d, B)
+        with np.errstate(all='ignore'):
+            mapped = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
+            mapped = np.where(np.isnan(mapped), 0, np.where(np.isinf(mapped), big, mapped))
+            delta = mapped - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype)
+        delta = np.where(np.isfinite(delta), delta, 0).astype(self.dtype)
+        return values_b, members, loc, obs, delta
+
+    def _chain_factor_block(self, obs, delta, Xd, N, d, K, kstride, W, a):
+        """ONE batched factorisation of a block's observation covariances (g3_gp_factor_batched_fields)"""
+        dev = self.device
+        dd = dev.upload(np.ascontiguousarray(delta))
+        try:
+            return dev.gp_factor_batched_fields(obs[0], obs[1], obs[2], Xd, N, d, dd, K, kstride, W, a)
+        finally:
+            dd.free()         # a (B, N) buffer per block: not left to the garbage collector over a long chain
+
     def _predict_chain_blocks(self, rows, space, inputs, outputs, switches, noise, prior, batch):
         """predict_chain for a plain Gaussian process: per block of `batch` rows ONE batched factorisation
         (g3_gp_factor_batched_fields) and ONE batched cross solve (g3_gp_cross_batched_fields: rectangular Gram with the
@@ -272,29 +303,12 @@ class GaussianProcess(EllipticalProcess):
             for lo in range(0, n_rows, batch):
                 hi = min(lo + batch, n_rows)
                 B = hi - lo
-                values_b, _ = self._values_rows(rows[lo:hi])
-                values0 = self._values_row(values_b, 0)
-                ctmpl, coffs, cfields = compile_spec_rows(kern_c.spec(values_b, d), kern_c.spec(values0, d), d, B)
-                with np.errstate(all='ignore'):
-                    loc = np.asarray(self.f_location.rows(S, values_b, B), dtype=self.dtype)
+                _, (ctmpl, coffs, cfields), loc, obs, delta = self._chain_block_members(rows[lo:hi], kern_c, S, X, y, prior)
                 if prior:
                     if need_var:
                         dev.gp_cross_batched_fields(ctmpl, coffs, cfields, Sd, M, Xd, M, d, None, 0, None, None, None, None, kd)
                 else:
-                    tmpl, offs, fields = compile_spec_rows(self.f_kernel_noise.spec(values_b, d),
-                                                           self.f_kernel_noise.spec(values0, d), d, B)
-                    with np.errstate(all='ignore'):
-                        # the posterior's delta: tt_to_num(mapping.inv(y)) - m(X) (elliptical.py:63), non-finite entries sent
-                        # as 0, exactly as _factor / _solve('post') prepare it for one row
-                        mapped = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
-                        mapped = np.where(np.isnan(mapped), 0, np.where(np.isinf(mapped), big, mapped))
-                        delta = mapped - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype)
-                    delta = np.where(np.isfinite(delta), delta, 0).astype(self.dtype)
-                    dd = dev.upload(np.ascontiguousarray(delta))
-                    try:
-                        dev.gp_factor_batched_fields(tmpl, offs, fields, Xd, N, d, dd, K, kstride, W, a)
-                    finally:
-                        dd.free()         # a (B, N) buffer per block: not left to the garbage collector over a long chain
+                    self._chain_factor_block(obs, delta, Xd, N, d, K, kstride, W, a)
                     dev.gp_cross_batched_fields(ctmpl, coffs, cfields, Sd, M, Xd, N, d, K, kstride, W, a,
                                                 mu if need_loc else None, ss if need_var else None, kd if need_var else None)
                     if need_loc:
@@ -327,6 +341,54 @@ class GaussianProcess(EllipticalProcess):
             if prior and kd is not None:
                 kd.free()
         return out
+
+    def _sample_chain_blocks(self, rows, space, inputs, outputs, rand, noise, prior, batch):
+        """sample_chain for a plain Gaussian process: per block of `batch` rows ONE batched factorisation and ONE
+        g3_gp_draws_batched_fields (cross solve that keeps V, posterior covariances through the batched MFMA product, the
+        jitter schedule per member on the device, the draws with the member in the grid); the host side is the rows'
+        location and the mapping's scrub, as th_location / th_mapping do for one row.  Returns (draws (rows, M, samples),
+        tries, fallback, jitter per row)."""
+        dev = self.device
+        big = self.dtype.type(np.float32(1e10))
+        S = self._x(self.space if space is None else space)
+        n_rows, M = len(rows), S.shape[0]
+        samples = rand.shape[2]
+        out = np.empty((n_rows, M, samples), dtype=self.dtype)
+        tries, fallback, jitter = np.zeros(n_rows, dtype=np.int32), np.zeros(n_rows, dtype=bool), np.zeros(n_rows)
+        kern = self.f_kernel_noise if noise else self.f_kernel           # elliptical.py:70,74,78-79
+        Sd = dev.upload(S)
+        Xd = None
+        if prior:
+            X = y = None
+            N, d, K, W, a, kstride = 0, S.shape[1], None, None, None, 0
+            batch = max(1, min(int(batch or _lib.G3_MAX_BATCH), n_rows, _lib.G3_MAX_BATCH))
+        else:
+            X = self._x(self.inputs if inputs is None else inputs)
+            y = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
+            N, d = X.shape
+            Np = _lib.roundup(N)
+            kstride = (Np + _lib.G3_RHS_PAD) * Np
+            if batch is None:     # per member: factor + right-hand-side block, block inverses, a (V, C and Lp live in the library)
+                batch = int((4e9 - 2 ** 28) // ((kstride + Np * _lib.G3_PAD + Np) * self.dtype.itemsize))
+            batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
+            Xd = dev.upload(X)
+            ws = self._chain_workspace(batch, Np, False)
+            K, W, a = ws['K'], ws['W'], ws['a']
+        try:
+            for lo in range(0, n_rows, batch):
+                hi = min(lo + batch, n_rows)
+                _, (tmpl, offs, fields), loc, obs, delta = self._chain_block_members(rows[lo:hi], kern, S, X, y, prior)
+                if not prior:
+                    self._chain_factor_block(obs, delta, Xd, N, d, K, kstride, W, a)
+                g, tries[lo:hi], fallback[lo:hi], jitter[lo:hi] = dev.gp_draws_batched_fields(
+                    tmpl, offs, fields, Sd, M, Xd, N, d, K, kstride, W, a, noise, loc, rand[lo:hi])
+                with np.errstate(all='ignore'):
+                    out[lo:hi] = np.where(np.isnan(g), 0, np.where(np.isinf(g), big, g))     # th_mapping scrubs its result
+        finally:
+            Sd.free()
+            if Xd is not None:
+                Xd.free()
+        return out, tries, fallback, jitter
 
     def dlogp_chain(self, chain, batch=None):
         """one dlogp per row of a flat-parameter chain, shape (rows, ndim) -- what fixed_dlogp averages

@@ -540,6 +540,58 @@ class StochasticProcess:
             out['mixture_variance'] = np.mean(pred['variance'], axis=0) + np.var(pred['mean'], axis=0)
         return out
 
+    # ---- draws over the rows of a chain (models.py:521-543: `particles`, a loop of single sampler calls over an MCMC trace)
+    def sample_chain(self, chain, space=None, inputs=None, outputs=None, samples=1, prior=False, noise=False, rand=None,
+                     batch=None, return_info=False):
+        """`sampler` for every row of a flat-parameter chain: (rows, M, samples), row i equal to
+        sampler(array_to_dict(chain[i]), ..., samples=samples, rand=rand[i]).  `rand` is (rows, M, samples); by default
+        np.random.randn(rows, M, samples), which takes from the global stream what the loop's successive randn(M, samples)
+        calls take.  A GaussianProcess draws `batch` rows at a time in batched launches (g3_gp_factor_batched_fields +
+        g3_gp_draws_batched_fields), every other process takes the loop.  return_info=True adds a DictObj of per-row
+        `tries`, `fallback`, `jitter` of the robust factorisation of the rows' covariances (None where the loop ran)."""
+        rows = self._chain_rows(chain)
+        prior = prior or not self.is_observed
+        space = self.space if space is None else space
+        n_rows, M, samples = len(rows), len(space), int(samples)
+        if rand is not None:
+            rand = np.asarray(rand, dtype=self.dtype)
+            if rand.shape != (n_rows, M, samples):
+                raise ValueError('rand must have shape (rows, len(space), samples) = %r, got %r'
+                                 % ((n_rows, M, samples), rand.shape))
+        info = DictObj(tries=None, fallback=None, jitter=None)
+        if n_rows and self._chain_predict_batched():
+            if rand is None:
+                rand = np.asarray(np.random.randn(n_rows, M, samples), dtype=self.dtype)
+            out, info['tries'], info['fallback'], info['jitter'] = self._sample_chain_blocks(
+                rows, space, inputs, outputs, rand, noise, prior, batch)
+        else:
+            out = np.empty((n_rows, M, samples), dtype=self.dtype)
+            for i, row in enumerate(rows):          # rand None: every sampler call draws its own, in the loop's order
+                out[i] = self.sampler(self.active.array_to_dict(row), space, inputs, outputs, samples=samples, prior=prior,
+                                      noise=noise, rand=None if rand is None else rand[i])
+        return (out, info) if return_info else out
+
+    def particles(self, chain, nsamples=None, *, space=None, inputs=None, outputs=None, samples=1, prior=False, noise=False,
+                  rand=None, batch=None):
+        """models.py:521-543: one set of `samples` joint draws per row of a chain (2-D array or anything with `.values`),
+        cycling over the rows until `nsamples` sets are taken (default: one per row), concatenated along axis 1 to
+        (M, nsamples * samples) -- the fully Bayesian predictive: hyper-parameter and function uncertainty together.
+        `rand`: (nsamples, M, samples) normals, one slice per set."""
+        rows = self._chain_rows(chain)
+        nsamples = len(rows) if nsamples is None else int(nsamples)
+        M = len(self.space if space is None else space)
+        if nsamples < 0 or (nsamples and not len(rows)):
+            raise ValueError('particles: %d draws asked of a chain of %d rows' % (nsamples, len(rows)))
+        if rand is not None and np.shape(rand) != (nsamples, M, int(samples)):
+            raise ValueError('rand must have shape (nsamples, len(space), samples) = %r, got %r'
+                             % ((nsamples, M, int(samples)), np.shape(rand)))
+        if not nsamples:
+            return np.empty((M, 0), dtype=self.dtype)
+        picked = rows[np.arange(nsamples) % len(rows)]
+        draws = self.sample_chain(picked, space=space, inputs=inputs, outputs=outputs, samples=samples, prior=prior, noise=noise,
+                                  rand=rand, batch=batch)
+        return np.concatenate(list(draws), axis=1)
+
     # ---- averages over a fixed chain (stochastic.py:522-564): the rows of active.fixed_chain with
     #      the sampling dimensions overwritten by `sampling_params`
     def _fixed_rows(self, sampling_params):

@@ -219,6 +219,19 @@ int g3_potrf_robust(g3_ctx* ctx, const void* K_dev, int64_t ldk, void* L_dev, in
                     int64_t n, g3_dtype dt, int maxtries, int* tries_host, int* fallback_host,
                     double* jitter_host);
 
+/* g3_potrf_robust for each of `batch` independent n x n matrices: K_b = K_dev + b * kstride (untouched), L_b = L_dev +
+ * b * lstride.  L_b is lower with the strict upper triangle AND everything beyond n zero within its roundup(n,128)-square
+ * slot (ldl >= roundup(n,128), lstride >= roundup(n,128) * ldl): what g3_gp_sample asks of a factor.  Never fails; the
+ * schedule is the reference's (tensors.py:203-222): dK = mean(diag) * 1e-6f, non-positive diagonals lifted, up to
+ * `maxtries` retries each x 10f, a non-finite input makes every retry fail, finally 1e-10f * I with fallback = 1.
+ * n <= 256: ONE launch, one workgroup per member runs the whole schedule on the device (its arithmetic is the one
+ * definition the single call uses) with the factorisation programs of g3_potrf at these sizes, and the batch's
+ * tries / fallback / jitter come back in one copy.  n > 256: the members go through g3_potrf_robust one by one inside
+ * this call.  batch <= 4096.  tries_host / fallback_host / jitter_host: `batch` entries each (any may be NULL). */
+int g3_potrf_robust_batched(g3_ctx* ctx, const void* K_dev, int64_t ldk, int64_t kstride, void* L_dev, int64_t ldl,
+                            int64_t lstride, int batch, int64_t n, g3_dtype dt, int maxtries, int* tries_host,
+                            int* fallback_host, double* jitter_host);
+
 /* Solve X * L^T = B in place (B is m x n: each ROW of B is one right-hand side, i.e.
  * B^T <- solve_lower_triangular(L, B^T); tensors.py:265-270, gaussian.py:212).
  * n a multiple of 128, m a multiple of 128.  invd_dev: block inverses from g3_potrf, or NULL to
@@ -432,6 +445,40 @@ int g3_gp_cross_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, int
                                const void* X_dev, int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl,
                                int64_t kstride, const void* invd_dev, const void* a_dev, g3_dtype dt, void* mu_dev,
                                void* ss_dev, void* kdiag_dev);
+
+/* One joint draw set per chain member, after g3_gp_factor_batched(_fields) on the same buffers: what the reference's
+ * `particles` (g3py/bayesian/models.py:521-543) gets from a Python loop of single sampler calls.  Per member b, with
+ * Mp = roundup(M,128):
+ *     V_b  = tt_to_num(prog_b(Xs, X)) L_b^-T          mu_b = V_b a_b
+ *     C_b  = P_b - V_b V_b^T,  P_b = prog_b(Xs, Xs)   (lift != 0 -- the noise kernel: P_b scrubbed and its non-positive
+ *                                                     diagonal lifted per member, tt_to_cov as g3_gram's SCRUB + g3_cov_lift)
+ *     Lp_b = cholesky_robust(C_b)                     (g3_potrf_robust_batched: the jitter schedule per member on the device
+ *                                                     for Mp <= 256)
+ *     out[b][i][s] = loc[b][i] + mu_b[i] + sum_j Lp_b[i][j] Z[b][j][s]
+ * loc_host (batch x M), Z_host (batch x M x S) and out_host (batch x M x S) are host arrays of the dtype, borrowed for the
+ * call, as in g3_gp_sample.  C_dev / Lp_dev (device, batch x Mp x Mp compact, either may be NULL) receive the lower
+ * triangle of C_b (its strict upper triangle is unspecified) and Lp_b (zero outside its M x M lower triangle).
+ * tries_host / fallback_host / jitter_host: per member, what the schedule did (any may be NULL).
+ * L_dev == NULL draws from the prior: C_b = P_b, no cross solve, and X_dev, N, ldx, ldl, kstride, invd_dev, a_dev are not
+ * looked at.  V_b, C_b and Lp_b live in the context's workspace, at most 256 MB of it per launch group: longer chains
+ * take several groups.  Members with roundup(N,128) > 1024 get V_b from the g3_gp_cross path one at a time, members with
+ * Mp > 256 their factor from g3_potrf_robust one at a time, inside this call.  A member whose observation factor went
+ * through the jitter schedule or the fallback is solved against the factor that was kept.  The row sums of mu and of
+ * the draws are combined in a fixed order: two calls give the same bits.  All programs share one structure;
+ * batch <= 4096; what g3_gp_cross_batched says about the factor buffers holds here too. */
+int g3_gp_draws_batched(g3_ctx* ctx, const g3_kernel_prog* progs_host, int batch, const void* Xs_dev, int64_t M, int64_t ldxs,
+                        const void* X_dev, int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl, int64_t kstride,
+                        const void* invd_dev, const void* a_dev, g3_dtype dt, int lift, const void* loc_host,
+                        const void* Z_host, int64_t S, void* out_host, void* C_dev, void* Lp_dev, int maxtries,
+                        int* tries_host, int* fallback_host, double* jitter_host);
+/* The same with the members given as template + per-member doubles, exactly as g3_gp_cross_batched_fields takes them (the
+ * offset of a G3_K_DOT exponent is refused).  Argument numbers in negative return codes follow this signature. */
+int g3_gp_draws_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, int batch, const double* fields_host,
+                               const int32_t* offsets_host, int nfield, const void* Xs_dev, int64_t M, int64_t ldxs,
+                               const void* X_dev, int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl,
+                               int64_t kstride, const void* invd_dev, const void* a_dev, g3_dtype dt, int lift,
+                               const void* loc_host, const void* Z_host, int64_t S, void* out_host, void* C_dev,
+                               void* Lp_dev, int maxtries, int* tries_host, int* fallback_host, double* jitter_host);
 
 /* Latent draws of the sampler (g3py/processes/gaussian.py:89-95, before the mapping):
  *     out[i][s] = loc[i] + sum_j L[i][j] Z[j][s]
