@@ -531,11 +531,17 @@ static int fetch_stats(g3_ctx* ctx, double* out, int cnt) {
   return G3_OK;
 }
 
-static int diag_stats_launch(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double* dout, int lift) {
+// one workgroup per member, members `stride` elements apart; the caller checks the launch
+static void diag_stats_members(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double* dout, int lift, int members,
+                               int64_t stride) {
   if (dt == G3_F64)
-    hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(1), dim3(1024), 0, ctx->stream, (double*)A, n, ld, dout, lift, (int64_t)0);
+    hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(members), dim3(1024), 0, ctx->stream, (double*)A, n, ld, dout, lift, stride);
   else
-    hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(1), dim3(1024), 0, ctx->stream, (float*)A, n, ld, dout, lift, (int64_t)0);
+    hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(members), dim3(1024), 0, ctx->stream, (float*)A, n, ld, dout, lift, stride);
+}
+
+static int diag_stats_launch(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double* dout, int lift) {
+  diag_stats_members(ctx, A, n, ld, dt, dout, lift, 1, 0);
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -929,22 +935,6 @@ static int ensure_bbuf(g3_ctx* ctx, size_t bytes) {
   return G3_OK;
 }
 
-// Where the members' programs come from: `batch` complete host programs, or ONE template plus, per member, the doubles
-// that differ (hyper-parameter values) and the byte offsets in g3_kernel_prog they go to -- a chain of 4096 members is
-// then 4096 x nfield doubles to pack and to copy instead of 4096 x 6 KB.
-struct MemberProgs {
-  const g3_kernel_prog* progs = nullptr;
-  const g3_kernel_prog* tmpl = nullptr;
-  const double* fields = nullptr;
-  const int32_t* offs = nullptr;
-  int nfield = 0;
-  void member(int b, g3_kernel_prog* out) const {
-    if (progs) { *out = progs[b]; return; }
-    *out = *tmpl;
-    for (int i = 0; i < nfield; ++i) memcpy((char*)out + offs[i], &fields[(size_t)b * nfield + i], sizeof(double));
-  }
-};
-
 __global__ void __launch_bounds__(256) expand_progs_kernel(g3_kernel_prog* dst, const g3_kernel_prog* tmpl,
                                                           const double* fields, const int32_t* offs, int nfield) {
   const uint32_t* s = (const uint32_t*)tmpl;
@@ -953,6 +943,38 @@ __global__ void __launch_bounds__(256) expand_progs_kernel(g3_kernel_prog* dst, 
   __syncthreads();
   for (int i = threadIdx.x; i < nfield; i += 256)
     *(double*)((char*)o + offs[i]) = fields[(size_t)blockIdx.x * nfield + i];
+}
+
+int g3i_upload_members(g3_ctx* ctx, const MemberProgs& mp, int batch, size_t stat_bytes, size_t tail_bytes, g3_dev_members* out) {
+  const G3hMemberLayout lo = g3h_member_layout(batch, mp.nfield, mp.progs != nullptr, stat_bytes, tail_bytes);
+  int rc = ensure_bbuf(ctx, lo.total);
+  if (rc) return rc;
+  char* base = (char*)ctx->bbuf;
+  out->progs = (g3_kernel_prog*)(base + lo.progs);
+  out->stats = (double*)(base + lo.stats);
+  out->tail = base + lo.tail;
+  if (mp.progs) {
+    G3_HIP(hipMemcpyAsync(out->progs, mp.progs, (size_t)batch * sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
+    return G3_OK;
+  }
+  G3_HIP(hipMemcpyAsync(base + lo.tmpl, mp.tmpl, sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
+  if (mp.nfield) {
+    G3_HIP(hipMemcpyAsync(base + lo.fields, mp.fields, (size_t)batch * mp.nfield * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    G3_HIP(hipMemcpyAsync(base + lo.offs, mp.offs, (size_t)mp.nfield * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  hipLaunchKernelGGL(expand_progs_kernel, dim3(batch), dim3(256), 0, ctx->stream, out->progs, (const g3_kernel_prog*)(base + lo.tmpl),
+                     (const double*)(base + lo.fields), (const int32_t*)(base + lo.offs), mp.nfield);
+  G3_LAUNCH_CHECK();
+  return G3_OK;
+}
+
+// the members' pivot flags of the factorisation just queued -> ctx->h_info (valid once the stream is synchronised), and the
+// device flags cleared for the next call: through g3i_reset_info inside the sweep's batch mode, else all `batch` directly
+static int read_member_flags(g3_ctx* ctx, int batch, bool in_batch_mode) {
+  if (hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    return G3_ERR_HIP;
+  if (in_batch_mode) return g3i_reset_info(ctx);
+  return hipMemsetAsync(ctx->d_info, 0, sizeof(int) * batch, ctx->stream) != hipSuccess ? G3_ERR_HIP : G3_OK;
 }
 
 static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, const void* X, int64_t N,
@@ -974,121 +996,68 @@ static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch,
   if (!invd) return -14;
   if (!a) return -15;
   if (!out) return -16;
-  g3_kernel_prog first;
-  mp.member(0, &first);
-  if (mp.progs) {
-    for (int b = 0; b < batch; ++b) {
-      if (g3i_validate_prog(&mp.progs[b], d)) return -2;
-      if (!g3h_same_structure(&mp.progs[0], &mp.progs[b])) return -2;
-    }
-  } else {
-    if (g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(&first, d)) return -2;
-  }
-  const g3_kernel_prog* progs = &first;   // the structure every member shares
-  int rc = G3_OK;
+  g3_kernel_prog first;                     // the structure every member shares
+  if (g3i_validate_members(mp, batch, d, &first)) return -2;
   if (batch == 1)
-    return gp_factor_impl(ctx, progs, X, N, ldx, d, delta, dt, K, ldk, invd, a, out, nullptr, nullptr, 0, 0, nullptr,
+    return gp_factor_impl(ctx, &first, X, N, ldx, d, delta, dt, K, ldk, invd, a, out, nullptr, nullptr, 0, 0, nullptr,
                           nullptr);
-  // device copies of the programs, then the per-member statistics
-  const size_t pbytes = (size_t)batch * sizeof(g3_kernel_prog);
+  // device copies of the programs, then the per-member statistics; behind them the cooperative kernel's control words
   const size_t sbytes = (size_t)batch * 4 * sizeof(double);
-  const size_t fbytes = mp.progs ? 0 : (size_t)batch * mp.nfield * sizeof(double);
-  const size_t obytes = mp.progs ? 0 : (((size_t)mp.nfield * sizeof(int32_t) + 15) & ~(size_t)15);
-  const size_t cbytes = g3i_coop_ctl_bytes(batch);
-  const size_t head = (pbytes + sbytes + (mp.progs ? 0 : sizeof(g3_kernel_prog)) + fbytes + obytes + 255) & ~(size_t)255;
-  rc = ensure_bbuf(ctx, head + cbytes);
+  g3_dev_members dm;
+  int rc = g3i_upload_members(ctx, mp, batch, sbytes, g3i_coop_ctl_bytes(batch), &dm);
   if (rc) return rc;
-  unsigned* coop_ctl = (unsigned*)((char*)ctx->bbuf + head);
-  g3_kernel_prog* dprogs = (g3_kernel_prog*)ctx->bbuf;
-  double* dstats = (double*)((char*)ctx->bbuf + pbytes);
-  if (mp.progs) {
-    G3_HIP(hipMemcpyAsync(dprogs, mp.progs, pbytes, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    g3_kernel_prog* dtmpl = (g3_kernel_prog*)((char*)dstats + sbytes);
-    double* dfields = (double*)(dtmpl + 1);
-    int32_t* doffs = (int32_t*)((char*)dfields + fbytes);
-    G3_HIP(hipMemcpyAsync(dtmpl, mp.tmpl, sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
-    if (mp.nfield) {
-      G3_HIP(hipMemcpyAsync(dfields, mp.fields, fbytes, hipMemcpyHostToDevice, ctx->stream));
-      G3_HIP(hipMemcpyAsync(doffs, mp.offs, (size_t)mp.nfield * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    hipLaunchKernelGGL(expand_progs_kernel, dim3(batch), dim3(256), 0, ctx->stream, dprogs, dtmpl, dfields, doffs, mp.nfield);
-    G3_LAUNCH_CHECK();
-  }
+  double* dstats = dm.stats;
   const int64_t wstride = Np * G3_LB;
   // K_b = tt_to_cov(cov(X)) (elliptical.py:70-71), right-hand-side block = [delta_b; 0]
   const unsigned nb = (unsigned)((Np + 255) / 256);
   char* rhs = (char*)K + (size_t)Np * ldk * es;
   const bool small = Np <= 2 * G3_LB;       // one workgroup per member does the whole evaluation (g3i_small_factor_batched)
   int pr = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)batch * ((double)N * d + 0.5 * (double)N * (N + 1)) * es);
-  rc = g3i_gram_batched(ctx, dprogs, progs, batch, X, N, ldx, d, dt, K, ldk, kstride, Np,
+  rc = g3i_gram_batched(ctx, dm.progs, &first, batch, X, N, ldx, d, dt, K, ldk, kstride, Np,
                         G3_GRAM_LOWER | G3_GRAM_SCRUB | G3_GRAM_PAD_EYE);
   if (rc) return rc;
-  if (small) {
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(batch), dim3(1024), 0, ctx->stream, (double*)K, N, ldk, (double*)nullptr, 1, kstride);
-    else
-      hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(batch), dim3(1024), 0, ctx->stream, (float*)K, N, ldk, (double*)nullptr, 1, kstride);
-    g3i_prof_end(ctx, pr);
-    G3_LAUNCH_CHECK();
-    pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)batch * ((double)N * N * N / 3.0 + (double)N * N));
-    rc = g3i_small_factor_batched(ctx, K, ldk, kstride, invd, wstride, delta, ldd, a, Np, dstats, batch, N, Np, dt);
-    g3i_prof_end(ctx, pr);
-    if (!rc && hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-      rc = G3_ERR_HIP;
-    if (!rc && hipMemsetAsync(ctx->d_info, 0, sizeof(int) * batch, ctx->stream) != hipSuccess) rc = G3_ERR_HIP;   // every member's flag
-    if (rc) return rc;
-  } else if (dt == G3_F64) {
-    hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(batch), dim3(1024), 0, ctx->stream, (double*)K, N, ldk,
-                       (double*)nullptr, 1, kstride);
-    hipLaunchKernelGGL((pad_row_kernel<double>), dim3(nb, batch), dim3(256), 0, ctx->stream, (double*)rhs, ldk,
-                       (const double*)delta, N, Np, RB, kstride, ldd);
-  } else {
-    hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(batch), dim3(1024), 0, ctx->stream, (float*)K, N, ldk,
-                       (double*)nullptr, 1, kstride);
-    hipLaunchKernelGGL((pad_row_kernel<float>), dim3(nb, batch), dim3(256), 0, ctx->stream, (float*)rhs, ldk,
-                       (const float*)delta, N, Np, RB, kstride, ldd);
-  }
+  diag_stats_members(ctx, K, N, ldk, dt, nullptr, 1, batch, kstride);
   if (!small) {
+    if (dt == G3_F64)
+      hipLaunchKernelGGL((pad_row_kernel<double>), dim3(nb, batch), dim3(256), 0, ctx->stream, (double*)rhs, ldk,
+                         (const double*)delta, N, Np, RB, kstride, ldd);
+    else
+      hipLaunchKernelGGL((pad_row_kernel<float>), dim3(nb, batch), dim3(256), 0, ctx->stream, (float*)rhs, ldk,
+                         (const float*)delta, N, Np, RB, kstride, ldd);
+  }
   g3i_prof_end(ctx, pr);
   G3_LAUNCH_CHECK();
   pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)batch * ((double)N * N * N / 3.0 + (double)N * N));
-  if (Np <= ctx->tune.coop_max_n && batch >= ctx->tune.coop_min_batch) {
+  if (small) {
+    rc = g3i_small_factor_batched(ctx, K, ldk, kstride, invd, wstride, delta, ldd, a, Np, dstats, batch, N, Np, dt);
+    g3i_prof_end(ctx, pr);
+    if (!rc) rc = read_member_flags(ctx, batch, false);
+  } else if (Np <= ctx->tune.coop_max_n && batch >= ctx->tune.coop_min_batch) {
     // long chains of medium members: a group of workgroups per member, the whole batch in ONE launch (g3_chainb.hip): 1.2 -
     // 1.3x the lock-step sweep below at N <= 512, 1.08x at 768 - 1024; short batches (< ~200 members) stay with the sweep,
     // whose launches are at least as wide as the batch (profiles/r05_chain_medium.txt)
-    rc = g3i_coop_factor_batched(ctx, K, ldk, kstride, invd, wstride, coop_ctl, batch, Np, dt);
+    rc = g3i_coop_factor_batched(ctx, K, ldk, kstride, invd, wstride, (unsigned*)dm.tail, batch, Np, dt);
     g3i_prof_end(ctx, pr);
-    if (!rc && hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-      rc = G3_ERR_HIP;
-    if (!rc && hipMemsetAsync(ctx->d_info, 0, sizeof(int) * batch, ctx->stream) != hipSuccess) rc = G3_ERR_HIP;   // every member's flag
-    if (rc) return rc;
+    if (!rc) rc = read_member_flags(ctx, batch, false);
   } else {
     // one sweep factors every member; a member whose pivot fails only stops its own launches
-    ctx->batch = batch;
-    ctx->bstride = kstride;
-    ctx->bstride_w = wstride;
-    ctx->bw_base = (const char*)invd;
-    ctx->bw_bytes = (size_t)batch * wstride * es;
+    g3_batch_scope mode(ctx, batch, kstride, wstride, invd, (size_t)batch * wstride * es);
     rc = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, RB);
     g3i_prof_end(ctx, pr);
-    if (!rc && hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-      rc = G3_ERR_HIP;
-    if (!rc) rc = g3i_reset_info(ctx);
-    ctx->batch = 0;
-    ctx->bw_base = nullptr;
-    if (rc) return rc;
+    if (!rc) rc = read_member_flags(ctx, batch, true);
   }
-  // a_b = first row of the solved right-hand-side block; log det and a^T a per member
-  G3_HIP(hipMemcpy2DAsync(a, (size_t)Np * es, rhs, (size_t)kstride * es, (size_t)Np * es, (size_t)batch,
-                          hipMemcpyDeviceToDevice, ctx->stream));
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((logp_terms_kernel<double>), dim3(batch), dim3(1024), 0, ctx->stream, (const double*)K, N, ldk,
-                       (const double*)a, dstats, kstride, Np);
-  else
-    hipLaunchKernelGGL((logp_terms_kernel<float>), dim3(batch), dim3(1024), 0, ctx->stream, (const float*)K, N, ldk,
-                       (const float*)a, dstats, kstride, Np);
-  G3_LAUNCH_CHECK();
+  if (rc) return rc;
+  if (!small) {
+    // a_b = first row of the solved right-hand-side block; log det and a^T a per member
+    G3_HIP(hipMemcpy2DAsync(a, (size_t)Np * es, rhs, (size_t)kstride * es, (size_t)Np * es, (size_t)batch,
+                            hipMemcpyDeviceToDevice, ctx->stream));
+    if (dt == G3_F64)
+      hipLaunchKernelGGL((logp_terms_kernel<double>), dim3(batch), dim3(1024), 0, ctx->stream, (const double*)K, N, ldk,
+                         (const double*)a, dstats, kstride, Np);
+    else
+      hipLaunchKernelGGL((logp_terms_kernel<float>), dim3(batch), dim3(1024), 0, ctx->stream, (const float*)K, N, ldk,
+                         (const float*)a, dstats, kstride, Np);
+    G3_LAUNCH_CHECK();
   }
   double* hst = (double*)malloc(sbytes);
   if (!hst) return G3_ERR_NOMEM;
@@ -1137,19 +1106,9 @@ extern "C" int g3_gp_factor_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tm
                                            int64_t kstride, void* invd, void* a, double* out) {
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
-  if (!tmpl) return -2;
-  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
-  if (nfield && (!fields || !offsets)) return -4;
-  for (int i = 0; i < nfield; ++i)
-    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
-  MemberProgs mp;
-  mp.tmpl = tmpl;
-  mp.fields = fields;
-  mp.offs = offsets;
-  mp.nfield = nfield;
-  // the shared checks number their arguments as g3_gp_factor_batched does: X and later sit three places further here
-  int rc = gp_factor_batched_impl(ctx, mp, batch, X, N, ldx, d, delta, ldd, dt, K, ldk, kstride, invd, a, out);
-  return (rc <= -4 && rc >= -16) ? rc - 3 : rc;
+  return g3i_fields_call(tmpl, batch, false, fields, offsets, nfield, -16, [&](const MemberProgs& mp) {
+    return gp_factor_batched_impl(ctx, mp, batch, X, N, ldx, d, delta, ldd, dt, K, ldk, kstride, invd, a, out);
+  });
 }
 
 extern "C" int g3_gp_factor(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X, int64_t N,
@@ -1193,6 +1152,32 @@ extern "C" int g3_gp_factor_predict(g3_ctx* ctx, const g3_kernel_prog* prog, con
   return gp_factor_impl(ctx, prog, X, N, ldx, d, delta, dt, K, ldk, invd, a, out, prog_cross, Xs, M, ldxs, mu, ss);
 }
 
+// One member's posterior cross pieces: V = tt_to_num(cov(Xs, X))  (elliptical.py:78-79), V <- V L^-T, then the row sums
+// mu = V a, ss = |rows of V|^2 where asked for.  g3_gp_cross, and the batched entry points for members beyond their
+// one-launch solve (Np > 1024); `tags`: only g3_gp_cross records the profiler's regions.
+static int cross_single(g3_ctx* ctx, const g3_kernel_prog* prog, const void* Xs, int64_t M, int64_t ldxs, const void* X, int64_t N,
+                        int64_t ldx, int d, const void* L, int64_t ldl, const void* invd, const void* a, g3_dtype dt, void* V,
+                        int64_t ldv, void* mu, void* ss, bool tags) {
+  const int64_t Np = g3_roundup(N, G3_LB), Mp = g3_roundup(M, 128);
+  const double es_d = (double)g3_esize(dt);
+  int pr = tags ? g3i_prof_begin(ctx, G3_TAG_CROSS_GRAM, (double)(N + M) * d * es_d + (double)N * M * es_d) : -1;
+  int rc = g3_gram(ctx, prog, Xs, M, ldxs, X, N, ldx, d, dt, V, ldv, Mp, Np, G3_GRAM_SCRUB);
+  g3i_prof_end(ctx, pr);
+  if (rc) return rc;
+  rc = g3i_reset_info(ctx);
+  if (rc) return rc;
+  pr = tags ? g3i_prof_begin(ctx, G3_TAG_TRSM, (double)N * N * M) : -1;
+  rc = g3i_trsm_rlt(ctx, L, Np, ldl, V, Mp, ldv, dt, invd);
+  g3i_prof_end(ctx, pr);
+  if (rc) return rc;
+  if (mu || ss) {
+    pr = tags ? g3i_prof_begin(ctx, G3_TAG_REDUCE, 2.0 * N * M) : -1;
+    rc = rows_dot_ss_launch(ctx, V, M, N, ldv, a, dt, mu, ss);
+    g3i_prof_end(ctx, pr);
+  }
+  return rc;
+}
+
 extern "C" int g3_gp_cross(g3_ctx* ctx, const g3_kernel_prog* prog, const void* Xs, int64_t M,
                            int64_t ldxs, const void* X, int64_t N, int64_t ldx, int d, const void* L,
                            int64_t ldl, const void* invd, const void* a, g3_dtype dt, void* V, int64_t ldv,
@@ -1205,30 +1190,13 @@ extern "C" int g3_gp_cross(g3_ctx* ctx, const g3_kernel_prog* prog, const void* 
   if (!X) return -6;
   if (N <= 0) return -7;
   if (!L) return -10;
-  const int64_t Np = g3_roundup(N, G3_LB), Mp = g3_roundup(M, 128);
+  const int64_t Np = g3_roundup(N, G3_LB);
   const int64_t al = 16 / (int64_t)g3_esize(dt);
   if (ldl < Np || ldl % al) return -11;
   if (!V) return -14;
   if (ldv < Np || ldv % al) return -15;
   if (!invd) return -12;
-  // V = tt_to_num(cov(Xs, X))  (elliptical.py:78-79), then V <- V L^-T
-  const double es_d = (double)g3_esize(dt);
-  int pr = g3i_prof_begin(ctx, G3_TAG_CROSS_GRAM, (double)(N + M) * d * es_d + (double)N * M * es_d);
-  int rc = g3_gram(ctx, prog, Xs, M, ldxs, X, N, ldx, d, dt, V, ldv, Mp, Np, G3_GRAM_SCRUB);
-  g3i_prof_end(ctx, pr);
-  if (rc) return rc;
-  rc = g3i_reset_info(ctx);
-  if (rc) return rc;
-  pr = g3i_prof_begin(ctx, G3_TAG_TRSM, (double)N * N * M);
-  rc = g3i_trsm_rlt(ctx, L, Np, ldl, V, Mp, ldv, dt, invd);
-  g3i_prof_end(ctx, pr);
-  if (rc) return rc;
-  if (mu || ss) {
-    pr = g3i_prof_begin(ctx, G3_TAG_REDUCE, 2.0 * N * M);
-    rc = rows_dot_ss_launch(ctx, V, M, N, ldv, a, dt, mu, ss);
-    g3i_prof_end(ctx, pr);
-  }
-  return rc;
+  return cross_single(ctx, prog, Xs, M, ldxs, X, N, ldx, d, L, ldl, invd, a, dt, V, ldv, mu, ss, true);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1252,13 +1220,7 @@ static int gp_cross_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, 
   if (ldx < d) return -9;
   if (dt != G3_F64 && dt != G3_F32) return -16;
   g3_kernel_prog first;
-  mp.member(0, &first);
-  if (mp.progs) {
-    for (int b = 0; b < batch; ++b)
-      if (g3i_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return -2;
-  } else if (g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(&first, d)) {
-    return -2;
-  }
+  if (g3i_validate_members(mp, batch, d, &first)) return -2;
   const int64_t Np = g3_roundup(N, G3_LB), Mp = g3_roundup(M, 128);
   const size_t es = g3_esize(dt);
   const int64_t al = 16 / (int64_t)es;
@@ -1271,31 +1233,13 @@ static int gp_cross_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, 
     if (mu && !a) return -15;
   }
   if (!solve && !kdiag) return G3_OK;
-  // device copies of the members' programs: whole programs, or -- as g3_gp_factor_batched_fields does -- the template and the
-  // batch x nfield doubles that differ, expanded on the device (a chain row costs nfield doubles of PCIe, not a 6 KB program).
-  // Members beyond the one-launch solve keep their V (Mp x Np) behind the programs in the same context buffer.
+  // device copies of the members' programs; members beyond the one-launch solve keep their V (Mp x Np) behind them in the
+  // same context buffer
   const bool big = solve && Np > 1024;
-  const size_t pbytes = (size_t)batch * sizeof(g3_kernel_prog);
-  const size_t fbytes = mp.progs ? 0 : (size_t)batch * mp.nfield * sizeof(double);
-  const size_t obytes = mp.progs ? 0 : (((size_t)mp.nfield * sizeof(int32_t) + 15) & ~(size_t)15);
-  const size_t head = (pbytes + (mp.progs ? 0 : sizeof(g3_kernel_prog)) + fbytes + obytes + 255) & ~(size_t)255;
-  int rc = ensure_bbuf(ctx, head + (big ? (size_t)Mp * Np * es : 0));
+  g3_dev_members dm;
+  int rc = g3i_upload_members(ctx, mp, batch, 0, big ? (size_t)Mp * Np * es : 0, &dm);
   if (rc) return rc;
-  g3_kernel_prog* dprogs = (g3_kernel_prog*)ctx->bbuf;
-  if (mp.progs) {
-    G3_HIP(hipMemcpyAsync(dprogs, mp.progs, pbytes, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    g3_kernel_prog* dtmpl = (g3_kernel_prog*)((char*)dprogs + pbytes);
-    double* dfields = (double*)(dtmpl + 1);
-    int32_t* doffs = (int32_t*)((char*)dfields + fbytes);
-    G3_HIP(hipMemcpyAsync(dtmpl, mp.tmpl, sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
-    if (mp.nfield) {
-      G3_HIP(hipMemcpyAsync(dfields, mp.fields, fbytes, hipMemcpyHostToDevice, ctx->stream));
-      G3_HIP(hipMemcpyAsync(doffs, mp.offs, (size_t)mp.nfield * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    hipLaunchKernelGGL(expand_progs_kernel, dim3(batch), dim3(256), 0, ctx->stream, dprogs, dtmpl, dfields, doffs, mp.nfield);
-    G3_LAUNCH_CHECK();
-  }
+  const g3_kernel_prog* dprogs = dm.progs;
   G3_HIP(hipStreamSynchronize(ctx->stream));          // the host arrays are borrowed for the call only
   if (kdiag) {
     rc = g3i_gram_diag_batched(ctx, dprogs, batch, Xs, M, ldxs, d, dt, kdiag, Mp);
@@ -1329,16 +1273,12 @@ static int gp_cross_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, 
     return G3_OK;
   }
   // members beyond the one-launch solve: the single-member path (Gram, recursive solve, row sums) once per member
-  void* V = (char*)ctx->bbuf + head;
   for (int b = 0; b < batch; ++b) {
     g3_kernel_prog mine;
     mp.member(b, &mine);
-    rc = g3_gram(ctx, &mine, Xs, M, ldxs, X, N, ldx, d, dt, V, Np, Mp, Np, G3_GRAM_SCRUB);
-    if (!rc) rc = g3i_reset_info(ctx);
-    if (!rc) rc = g3i_trsm_rlt(ctx, (const char*)L + (size_t)b * kstride * es, Np, ldl, V, Mp, Np, dt,
-                               (const char*)invd + (size_t)b * wstride * es);
-    if (!rc) rc = rows_dot_ss_launch(ctx, V, M, N, Np, a ? (const char*)a + (size_t)b * Np * es : nullptr, dt,
-                                     mu ? (char*)mu + (size_t)b * Mp * es : nullptr, ss ? (char*)ss + (size_t)b * Mp * es : nullptr);
+    rc = cross_single(ctx, &mine, Xs, M, ldxs, X, N, ldx, d, (const char*)L + (size_t)b * kstride * es, ldl,
+                      (const char*)invd + (size_t)b * wstride * es, a ? (const char*)a + (size_t)b * Np * es : nullptr, dt, dm.tail, Np,
+                      mu ? (char*)mu + (size_t)b * Mp * es : nullptr, ss ? (char*)ss + (size_t)b * Mp * es : nullptr, false);
     if (rc) return rc;
   }
   return G3_OK;
@@ -1364,19 +1304,9 @@ extern "C" int g3_gp_cross_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmp
                                           void* kdiag) {
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
-  if (!tmpl) return -2;
-  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
-  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
-  if (nfield && (!fields || !offsets)) return -4;
-  for (int i = 0; i < nfield; ++i)
-    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
-  MemberProgs mp;
-  mp.tmpl = tmpl;
-  mp.fields = fields;
-  mp.offs = offsets;
-  mp.nfield = nfield;
-  const int rc = gp_cross_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, mu, ss, kdiag);
-  return (rc <= -4 && rc >= -19) ? rc - 3 : rc;
+  return g3i_fields_call(tmpl, batch, true, fields, offsets, nfield, -19, [&](const MemberProgs& mp) {
+    return gp_cross_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, mu, ss, kdiag);
+  });
 }
 
 
@@ -1421,35 +1351,12 @@ static int gp_draws_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, 
   if (!out) return -21;
   if (maxtries < 0) return -24;
   g3_kernel_prog first;
-  mp.member(0, &first);
-  if (mp.progs) {
-    for (int b = 0; b < batch; ++b)
-      if (g3i_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return -2;
-  } else if (g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(&first, d)) {
-    return -2;
-  }
+  if (g3i_validate_members(mp, batch, d, &first)) return -2;
   // device copies of the members' programs, as g3_gp_cross_batched makes them
-  const size_t pbytes = (size_t)batch * sizeof(g3_kernel_prog);
-  const size_t fbytes = mp.progs ? 0 : (size_t)batch * mp.nfield * sizeof(double);
-  const size_t obytes = mp.progs ? 0 : (((size_t)mp.nfield * sizeof(int32_t) + 15) & ~(size_t)15);
-  const size_t head = (pbytes + (mp.progs ? 0 : sizeof(g3_kernel_prog)) + fbytes + obytes + 255) & ~(size_t)255;
-  int rc = ensure_bbuf(ctx, head);
+  g3_dev_members dm;
+  int rc = g3i_upload_members(ctx, mp, batch, 0, 0, &dm);
   if (rc) return rc;
-  g3_kernel_prog* dprogs = (g3_kernel_prog*)ctx->bbuf;
-  if (mp.progs) {
-    G3_HIP(hipMemcpyAsync(dprogs, mp.progs, pbytes, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    g3_kernel_prog* dtmpl = (g3_kernel_prog*)((char*)dprogs + pbytes);
-    double* dfields = (double*)(dtmpl + 1);
-    int32_t* doffs = (int32_t*)((char*)dfields + fbytes);
-    G3_HIP(hipMemcpyAsync(dtmpl, mp.tmpl, sizeof(g3_kernel_prog), hipMemcpyHostToDevice, ctx->stream));
-    if (mp.nfield) {
-      G3_HIP(hipMemcpyAsync(dfields, mp.fields, fbytes, hipMemcpyHostToDevice, ctx->stream));
-      G3_HIP(hipMemcpyAsync(doffs, mp.offs, (size_t)mp.nfield * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    hipLaunchKernelGGL(expand_progs_kernel, dim3(batch), dim3(256), 0, ctx->stream, dprogs, dtmpl, dfields, doffs, mp.nfield);
-    G3_LAUNCH_CHECK();
-  }
+  const g3_kernel_prog* dprogs = dm.progs;
   G3_HIP(hipStreamSynchronize(ctx->stream));          // the host arrays are borrowed for the call only
   // the workspace of one launch group of cb members: [scratch of the single robust call] V C Lp mu loc Z out res [inverses]
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -1503,38 +1410,24 @@ static int gp_draws_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, 
       for (int b = 0; b < nb && !rc; ++b) {
         g3_kernel_prog pb;
         mp.member((int)b0 + b, &pb);
-        char* Vb = V + (size_t)b * v1;
-        rc = g3_gram(ctx, &pb, Xs, M, ldxs, X, N, ldx, d, dt, Vb, Np, Mp, Np, G3_GRAM_SCRUB);
-        if (!rc) rc = g3i_reset_info(ctx);
-        if (!rc) rc = g3i_trsm_rlt(ctx, (const char*)L + (size_t)(b0 + b) * kstride * es, Np, ldl, Vb, Mp, Np, dt,
-                                   (const char*)invd + (size_t)(b0 + b) * wstride * es);
-        if (!rc) rc = rows_dot_ss_launch(ctx, Vb, M, N, Np, (const char*)a + (size_t)(b0 + b) * Np * es, dt, mu + (size_t)b * m1, nullptr);
+        rc = cross_single(ctx, &pb, Xs, M, ldxs, X, N, ldx, d, (const char*)L + (size_t)(b0 + b) * kstride * es, ldl,
+                          (const char*)invd + (size_t)(b0 + b) * wstride * es, (const char*)a + (size_t)(b0 + b) * Np * es, dt,
+                          V + (size_t)b * v1, Np, mu + (size_t)b * m1, nullptr, false);
       }
       if (rc) break;
     }
     // P_b = prog_b(Xs, Xs); with the noise kernel tt_to_cov: scrubbed, non-positive diagonal lifted (elliptical.py:70,74)
     int pr = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)nb * ((double)M * d + 0.5 * (double)M * (M + 1)) * es);
     rc = g3i_gram_batched(ctx, dp, &mine, nb, Xs, M, ldxs, d, dt, Cb, Mp, Mp * Mp, Mp, G3_GRAM_LOWER | (lift ? G3_GRAM_SCRUB : 0u));
-    if (!rc && lift) {
-      if (dt == G3_F64)
-        hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(nb), dim3(1024), 0, ctx->stream, (double*)Cb, M, Mp, (double*)nullptr, 1, Mp * Mp);
-      else
-        hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(nb), dim3(1024), 0, ctx->stream, (float*)Cb, M, Mp, (double*)nullptr, 1, Mp * Mp);
-    }
+    if (!rc && lift) diag_stats_members(ctx, Cb, M, Mp, dt, nullptr, 1, nb, Mp * Mp);
     g3i_prof_end(ctx, pr);
     if (rc) break;
     if (hipGetLastError() != hipSuccess) { rc = G3_ERR_HIP; break; }
     if (post) {
-      ctx->batch = nb;                      // (set first: the flags of all nb members are cleared)
+      // batch mode first: g3i_reset_info then clears the flags of all nb members; V plays the block-inverse region
+      g3_batch_scope mode(ctx, nb, Mp * Mp, Mp * Np, V, (size_t)nb * v1);
       rc = g3i_reset_info(ctx);
-      if (rc) { ctx->batch = 0; break; }
-      ctx->bstride = Mp * Mp;
-      ctx->bstride_w = Mp * Np;
-      ctx->bw_base = V;
-      ctx->bw_bytes = (size_t)nb * v1;
-      rc = g3i_gemm_nt(ctx, Cb, Mp, V, Np, V, Np, Mp, Mp, Np, -1.0, 1.0, dt, 1);          // lower(C_b) -= V_b V_b^T  (elliptical.py:86-91)
-      ctx->batch = 0;
-      ctx->bw_base = nullptr;
+      if (!rc) rc = g3i_gemm_nt(ctx, Cb, Mp, V, Np, V, Np, Mp, Mp, Np, -1.0, 1.0, dt, 1);          // lower(C_b) -= V_b V_b^T  (elliptical.py:86-91)
       if (rc) break;
     }
     int* tr = tries_host ? tries_host + b0 : nullptr;
@@ -1596,20 +1489,10 @@ extern "C" int g3_gp_draws_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmp
                                           int* tries_host, int* fallback_host, double* jitter_host) {
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
-  if (!tmpl) return -2;
-  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
-  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
-  if (nfield && (!fields || !offsets)) return -4;
-  for (int i = 0; i < nfield; ++i)
-    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
-  MemberProgs mp;
-  mp.tmpl = tmpl;
-  mp.fields = fields;
-  mp.offs = offsets;
-  mp.nfield = nfield;
-  const int rc = gp_draws_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, lift, loc, Z, S, out,
-                                       C_dev, Lp_dev, maxtries, tries_host, fallback_host, jitter_host);
-  return (rc <= -4 && rc >= -24) ? rc - 3 : rc;
+  return g3i_fields_call(tmpl, batch, true, fields, offsets, nfield, -24, [&](const MemberProgs& mp) {
+    return gp_draws_batched_impl(ctx, mp, batch, Xs, M, ldxs, X, N, ldx, d, L, ldl, kstride, invd, a, dt, lift, loc, Z, S, out, C_dev,
+                                 Lp_dev, maxtries, tries_host, fallback_host, jitter_host);
+  });
 }
 
 // draws = loc + L Z  (gaussian.py:92-95).  Z^T and the product live in the context's workspace.

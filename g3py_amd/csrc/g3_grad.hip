@@ -13,6 +13,7 @@
 //                    the kernel expression per pair and accumulates G_ij * d k_ij / d theta for
 //                    every parameter of every leaf; deterministic two-stage reduction.
 #include "g3_internal.h"
+#include <optional>
 #include <vector>
 #include <stdlib.h>
 
@@ -1239,22 +1240,18 @@ extern "C" int g3_gp_dlogp_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int
   if (!Kinv_dev) return -16;
   if (!alpha_dev) return -17;
   if (!out_host) return -18;
-  if (batch > 1) {
-    ctx->batch = batch;
-    ctx->bstride = kstride;
-    ctx->bstride_w = Np * G3_LB;
-    ctx->bw_base = (const char*)invd_dev;
-    ctx->bw_bytes = (size_t)batch * Np * G3_LB * es;
+  int rc;
+  {
+    std::optional<g3_batch_scope> mode;       // one member: the plain single-member launches
+    if (batch > 1) mode.emplace(ctx, batch, kstride, Np * G3_LB, invd_dev, (size_t)batch * Np * G3_LB * es);
+    // in batch mode: EVERY member's pivot flag (a member whose first factorisation failed was re-run through the jitter
+    // schedule on its own, and its flag of the batched sweep must not turn this sweep's launches into no-ops for it)
+    rc = g3i_reset_info(ctx);
+    if (rc) return rc;
+    const int rec = g3i_prof_begin(ctx, G3_TAG_POTRF, 2.0 * (double)batch * (double)N * N * N / 3.0);
+    rc = g3i_potri(ctx, L_dev, Np, ldl, invd_dev, dt, Y_dev, ldl, Kinv_dev, ldl);
+    g3i_prof_end(ctx, rec);
   }
-  // in batch mode: EVERY member's pivot flag (a member whose first factorisation failed was re-run through the jitter
-  // schedule on its own, and its flag of the batched sweep must not turn this sweep's launches into no-ops for it)
-  int rc = g3i_reset_info(ctx);
-  if (rc) { ctx->batch = 0; ctx->bw_base = nullptr; return rc; }
-  const int rec = g3i_prof_begin(ctx, G3_TAG_POTRF, 2.0 * (double)batch * (double)N * N * N / 3.0);
-  rc = g3i_potri(ctx, L_dev, Np, ldl, invd_dev, dt, Y_dev, ldl, Kinv_dev, ldl);
-  g3i_prof_end(ctx, rec);
-  ctx->batch = 0;
-  ctx->bw_base = nullptr;
   if (rc) return rc;
   // alpha_b = L_b^-T a_b for every member in one launch, then the kernel-parameter sums of all members in launches that
   // carry the member in grid.y and ONE copy back (a chain of 4096 members: 3 launches instead of 12 288 and 4096 host waits)
@@ -1272,19 +1269,12 @@ extern "C" int g3_gp_dlogp_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmp
                                           const void* invd_dev, const void* a_dev, g3_dtype dt, void* Y_dev, void* Kinv_dev,
                                           void* alpha_dev, double* out_host) {
   if (!ctx) return -1;
-  if (!tmpl) return -2;
-  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
-  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
-  if (nfield && (!fields || !offsets)) return -4;
-  for (int i = 0; i < nfield; ++i)
-    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;      // the same rule as g3_gp_factor_batched_fields (g3_host.h)
-  std::vector<g3_kernel_prog> progs((size_t)batch, *tmpl);
-  for (int b = 0; b < batch; ++b)
-    for (int i = 0; i < nfield; ++i)
-      memcpy((char*)&progs[b] + offsets[i], &fields[(size_t)b * nfield + i], sizeof(double));
-  const int rc = g3_gp_dlogp_batched(ctx, progs.data(), batch, map, X_dev, N, ldx, d, L_dev, ldl, kstride, invd_dev, a_dev, dt,
-                                     Y_dev, Kinv_dev, alpha_dev, out_host);
-  return (rc <= -4 && rc >= -18) ? rc - 3 : rc;
+  return g3i_fields_call(tmpl, batch, true, fields, offsets, nfield, -18, [&](const MemberProgs& mp) {
+    std::vector<g3_kernel_prog> progs((size_t)batch);
+    for (int b = 0; b < batch; ++b) mp.member(b, &progs[b]);
+    return g3_gp_dlogp_batched(ctx, progs.data(), batch, map, X_dev, N, ldx, d, L_dev, ldl, kstride, invd_dev, a_dev, dt, Y_dev,
+                               Kinv_dev, alpha_dev, out_host);
+  });
 }
 
 extern "C" int g3_grad_path_stats(g3_ctx* ctx, double out_host[3]) {

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
@@ -586,4 +587,40 @@ static inline int g3h_field_offset_ok_tmpl(const g3_kernel_prog* tmpl, int32_t o
     if (in == offsetof(g3_leaf, freq) && tmpl->leaf[l].kind == G3_K_DOT) return 0;
   }
   return 1;
+}
+
+// Where the members' programs come from: `batch` complete host programs, or ONE template plus, per member, the doubles
+// that differ (hyper-parameter values) and the byte offsets in g3_kernel_prog they go to -- a chain of 4096 members is
+// then 4096 x nfield doubles to pack and to copy instead of 4096 x 6 KB.
+struct MemberProgs {
+  const g3_kernel_prog* progs = nullptr;
+  const g3_kernel_prog* tmpl = nullptr;
+  const double* fields = nullptr;
+  const int32_t* offs = nullptr;
+  int nfield = 0;
+  void member(int b, g3_kernel_prog* out) const {
+    if (progs) { *out = progs[b]; return; }
+    *out = *tmpl;
+    for (int i = 0; i < nfield; ++i) memcpy((char*)out + offs[i], &fields[(size_t)b * nfield + i], sizeof(double));
+  }
+};
+
+// Byte offsets of what a batched entry point keeps in the context's device buffer: the members' programs, `stat_bytes` of
+// per-member statistics (the factor path's 4 doubles each), then -- template form only (`whole` = 0) -- the template, the
+// batch x nfield doubles and the offsets table (rounded up to 16 bytes); the caller's `tail_bytes` start at the next
+// multiple of 256.  In the whole-programs form the three template regions are empty and sit at the end of the statistics.
+struct G3hMemberLayout {
+  size_t progs, stats, tmpl, fields, offs, tail, total;
+};
+static inline G3hMemberLayout g3h_member_layout(int batch, int nfield, int whole, size_t stat_bytes, size_t tail_bytes) {
+  G3hMemberLayout lo;
+  lo.progs = 0;
+  lo.stats = (size_t)batch * sizeof(g3_kernel_prog);
+  lo.tmpl = lo.stats + stat_bytes;
+  lo.fields = lo.tmpl + (whole ? 0 : sizeof(g3_kernel_prog));
+  lo.offs = lo.fields + (whole ? 0 : (size_t)batch * nfield * sizeof(double));
+  const size_t obytes = whole ? 0 : (((size_t)nfield * sizeof(int32_t) + 15) & ~(size_t)15);
+  lo.tail = (lo.offs + obytes + 255) & ~(size_t)255;
+  lo.total = lo.tail + tail_bytes;
+  return lo;
 }

@@ -133,6 +133,25 @@ static inline int64_t g3_bstride_of(const g3_ctx* ctx, const void* p) {
   return (ctx->bw_base && c >= ctx->bw_base && c < ctx->bw_base + ctx->bw_bytes) ? ctx->bstride_w : ctx->bstride;
 }
 
+// Batch mode for the launches issued while the object lives: members `stride` elements apart, operands inside
+// [w_base, +w_bytes) `stride_w` apart.  Every way out of the scope leaves the context in single-member mode.
+struct g3_batch_scope {
+  g3_ctx* ctx;
+  g3_batch_scope(g3_ctx* c, int batch, int64_t stride, int64_t stride_w, const void* w_base, size_t w_bytes) : ctx(c) {
+    ctx->batch = batch;
+    ctx->bstride = stride;
+    ctx->bstride_w = stride_w;
+    ctx->bw_base = (const char*)w_base;
+    ctx->bw_bytes = w_bytes;
+  }
+  ~g3_batch_scope() {
+    ctx->batch = 0;
+    ctx->bw_base = nullptr;
+  }
+  g3_batch_scope(const g3_batch_scope&) = delete;
+  g3_batch_scope& operator=(const g3_batch_scope&) = delete;
+};
+
 // launches issued now go to the low-priority bulk stream of the look-ahead sweep
 static inline bool g3_on_bulk_stream(const g3_ctx* ctx) {
 #ifdef G3_CHAIN_SERVER
@@ -274,3 +293,46 @@ int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_p
                  int64_t n2pad, unsigned flags, int sym, int64_t kstride, int64_t diag_off, dim3 grid);
 int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* invd, g3_dtype dt, void* Y,
               int64_t ldy, void* C, int64_t ldc);
+
+// ---- the members of a chain (MemberProgs, g3_host.h) as the batched entry points use them
+// Every member must be a valid program of ONE structure (whole programs), or the template and member 0 valid (template form:
+// the fields' offsets cannot touch structure).  0 and *first = member 0, the structure all share; 1 = refuse (status -2).
+static inline int g3i_validate_members(const MemberProgs& mp, int batch, int d, g3_kernel_prog* first) {
+  mp.member(0, first);
+  if (!mp.progs) return g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(first, d);
+  for (int b = 0; b < batch; ++b)
+    if (g3i_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return 1;
+  return 0;
+}
+
+// Device copies of the members' programs in ctx->bbuf (laid out by g3h_member_layout): whole programs in one copy, or the
+// template and the batch x nfield doubles that differ, expanded on the device -- a chain row costs nfield doubles of PCIe,
+// not a 6 KB program.  Queued on ctx->stream without a wait: the host arrays must stay until the caller has synchronised.
+struct g3_dev_members {
+  g3_kernel_prog* progs;
+  double* stats;   // stat_bytes behind the programs
+  void* tail;      // tail_bytes, 256-byte aligned
+};
+int g3i_upload_members(g3_ctx* ctx, const MemberProgs& mp, int batch, size_t stat_bytes, size_t tail_bytes, g3_dev_members* out);
+
+// The *_batched_fields entry points: the template form's own argument checks, then `call(members)` -- the implementation the
+// whole-programs entry point shares, whose checks number their arguments as that entry point does: the codes lo .. -4 name
+// arguments that sit three places further in the _fields signature.  check_batch: batch is refused here, before the fields
+// (g3_gp_factor_batched_fields leaves it to the shared checks, after them).
+template <typename F>
+static inline int g3i_fields_call(const g3_kernel_prog* tmpl, int batch, bool check_batch, const double* fields,
+                                  const int32_t* offsets, int nfield, int lo, F&& call) {
+  if (!tmpl) return -2;
+  if (check_batch && (batch < 1 || batch > G3_MAX_BATCH)) return -3;
+  if (nfield < 0 || nfield > G3_MAX_FIELDS) return -6;
+  if (nfield && (!fields || !offsets)) return -4;
+  for (int i = 0; i < nfield; ++i)
+    if (!g3h_field_offset_ok_tmpl(tmpl, offsets[i])) return -5;
+  MemberProgs mp;
+  mp.tmpl = tmpl;
+  mp.fields = fields;
+  mp.offs = offsets;
+  mp.nfield = nfield;
+  const int rc = call(mp);
+  return (rc <= -4 && rc >= lo) ? rc - 3 : rc;
+}

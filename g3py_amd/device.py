@@ -312,17 +312,36 @@ class Device:
         return dict(logdet=out[0], quad=out[1], nonfinite=out[2], tries=int(out[3]),
                     fallback=bool(out[4]), info=int(out[5]))
 
+    @staticmethod
+    def _progs(progs):
+        """the members' programs as a ctypes array: a list of KernelProg, or an array packed earlier (long chains: packing
+        4096 programs costs more than evaluating them)"""
+        return progs if isinstance(progs, C.Array) else (_lib.KernelProg * len(progs))(*progs)
+
+    @staticmethod
+    def _fields_args(name, tmpl, offsets, fields):
+        """the members as template + fields (see compile_spec_rows): the leading arguments of a g3_*_batched_fields call
+        behind the context, up to nfield (the two pointers keep the converted arrays alive), and the number of rows"""
+        fields = np.ascontiguousarray(fields, dtype=np.float64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        B, nf = fields.shape
+        if len(offsets) != nf:
+            raise G3Error('%s: %d offsets for %d fields' % (name, len(offsets), nf))
+        return B, (C.byref(tmpl), B, fields.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), nf)
+
+    @staticmethod
+    def _factor_args(B, X, N, d, delta, K, kstride, W, a):
+        out = np.empty((B, 6))
+        return out, (X.ptr, N, X.ld, d, delta.ptr, delta.ld, _lib.dtype_code(K.dtype), K.ptr, K.ld, kstride, W.ptr, a.ptr,
+                     out.ctypes.data_as(C.POINTER(C.c_double)))
+
     def gp_factor_batched(self, progs, X, N, d, delta, K, kstride, W, a, raw=False):
         """len(progs) evaluations in one sweep; K holds the members `kstride` elements apart.  `progs`: a list of
-        KernelProg or an existing ctypes array of them (long chains: packing 4096 programs costs more than evaluating
-        them); raw=True returns the (B, 6) array [logdet, quad, nonfinite, tries, fallback, info] instead of dicts"""
-        B = len(progs)
-        arr = progs if isinstance(progs, C.Array) else (_lib.KernelProg * B)(*progs)
-        out = np.empty((B, 6))
-        rc = self.lib.g3_gp_factor_batched(self.ctx, arr, B, X.ptr, N, X.ld, d, delta.ptr, delta.ld,
-                                           _lib.dtype_code(K.dtype), K.ptr, K.ld, kstride, W.ptr, a.ptr,
-                                           out.ctypes.data_as(C.POINTER(C.c_double)))
-        _check(self, rc, 'g3_gp_factor_batched')
+        KernelProg or an existing ctypes array of them; raw=True returns the (B, 6) array
+        [logdet, quad, nonfinite, tries, fallback, info] instead of dicts"""
+        arr = self._progs(progs)
+        out, args = self._factor_args(len(arr), X, N, d, delta, K, kstride, W, a)
+        _check(self, self.lib.g3_gp_factor_batched(self.ctx, arr, len(arr), *args), 'g3_gp_factor_batched')
         if raw:
             return out
         return [dict(logdet=r[0], quad=r[1], nonfinite=r[2], tries=int(r[3]), fallback=bool(r[4]), info=int(r[5]))
@@ -332,17 +351,9 @@ class Device:
         """gp_factor_batched with the members given as one template program plus a (B, nfield) float64 matrix of the
         values that differ and the byte offsets in g3_kernel_prog they belong at (see compile_spec_rows); the library
         expands the programs on the device.  Returns the raw (B, 6) statistics."""
-        fields = np.ascontiguousarray(fields, dtype=np.float64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        B, nf = fields.shape
-        if len(offsets) != nf:
-            raise G3Error('gp_factor_batched_fields: %d offsets for %d fields' % (len(offsets), nf))
-        out = np.empty((B, 6))
-        rc = self.lib.g3_gp_factor_batched_fields(self.ctx, C.byref(tmpl), B, fields.ctypes.data, offsets.ctypes.data, nf,
-                                                  X.ptr, N, X.ld, d, delta.ptr, delta.ld, _lib.dtype_code(K.dtype),
-                                                  K.ptr, K.ld, kstride, W.ptr, a.ptr,
-                                                  out.ctypes.data_as(C.POINTER(C.c_double)))
-        _check(self, rc, 'g3_gp_factor_batched_fields')
+        B, members = self._fields_args('gp_factor_batched_fields', tmpl, offsets, fields)
+        out, args = self._factor_args(B, X, N, d, delta, K, kstride, W, a)
+        _check(self, self.lib.g3_gp_factor_batched_fields(self.ctx, *members, *args), 'g3_gp_factor_batched_fields')
         return out
 
     def gp_cross(self, prog, Xs, M, X, N, d, L, W, a, V, mu, ss):
@@ -355,32 +366,25 @@ class Device:
     def _ptr(a):
         return a.ptr if a is not None else None
 
+    def _cross_args(self, Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag):
+        out = next(o for o in (mu, ss, kdiag) if o is not None)
+        return (Xs.ptr, M, Xs.ld, X.ptr, N, X.ld, d, self._ptr(K), K.ld if K is not None else 0, kstride, self._ptr(W),
+                self._ptr(a), _lib.dtype_code(out.dtype), self._ptr(mu), self._ptr(ss), self._ptr(kdiag))
+
     def gp_cross_batched(self, progs, Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag):
         """after gp_factor_batched on the same buffers: per member b, mu[b] = V_b a_b, ss[b] = |rows of V_b|^2 for
         V_b = K_b(Xs, X) L_b^-T and kdiag[b] = diag K_b(Xs, Xs), each a device (B, roundup(M, 128)) matrix or None.
         With mu and ss both None the factor buffers K, W, a may be None too (the prior needs no factorisation)."""
-        B = len(progs)
-        arr = progs if isinstance(progs, C.Array) else (_lib.KernelProg * B)(*progs)
-        out = next(o for o in (mu, ss, kdiag) if o is not None)
-        rc = self.lib.g3_gp_cross_batched(self.ctx, arr, B, Xs.ptr, M, Xs.ld, X.ptr, N, X.ld, d, self._ptr(K),
-                                          K.ld if K is not None else 0, kstride, self._ptr(W), self._ptr(a),
-                                          _lib.dtype_code(out.dtype), self._ptr(mu), self._ptr(ss), self._ptr(kdiag))
-        _check(self, rc, 'g3_gp_cross_batched')
+        arr = self._progs(progs)
+        args = self._cross_args(Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag)
+        _check(self, self.lib.g3_gp_cross_batched(self.ctx, arr, len(arr), *args), 'g3_gp_cross_batched')
 
     def gp_cross_batched_fields(self, tmpl, offsets, fields, Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag):
         """gp_cross_batched for members given as template + fields (see compile_spec_rows), after
         gp_factor_batched_fields on the same buffers"""
-        fields = np.ascontiguousarray(fields, dtype=np.float64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        B, nf = fields.shape
-        if len(offsets) != nf:
-            raise G3Error('gp_cross_batched_fields: %d offsets for %d fields' % (len(offsets), nf))
-        out = next(o for o in (mu, ss, kdiag) if o is not None)
-        rc = self.lib.g3_gp_cross_batched_fields(self.ctx, C.byref(tmpl), B, fields.ctypes.data, offsets.ctypes.data, nf,
-                                                 Xs.ptr, M, Xs.ld, X.ptr, N, X.ld, d, self._ptr(K),
-                                                 K.ld if K is not None else 0, kstride, self._ptr(W), self._ptr(a),
-                                                 _lib.dtype_code(out.dtype), self._ptr(mu), self._ptr(ss), self._ptr(kdiag))
-        _check(self, rc, 'g3_gp_cross_batched_fields')
+        _, members = self._fields_args('gp_cross_batched_fields', tmpl, offsets, fields)
+        args = self._cross_args(Xs, M, X, N, d, K, kstride, W, a, mu, ss, kdiag)
+        _check(self, self.lib.g3_gp_cross_batched_fields(self.ctx, *members, *args), 'g3_gp_cross_batched_fields')
 
     def _draws_args(self, Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm, Lp, maxtries):
         dtype = Xs.dtype
@@ -403,7 +407,7 @@ class Device:
         Lp_b = cholesky_robust(K_b(Xs, Xs) - V_b V_b^T) (lift: the noise kernel's tt_to_cov on K_b(Xs, Xs)).  loc (B, M) and
         Z (B, M, S) are host arrays; Cm / Lp: optional device (B * Mp, Mp) buffers for the covariances and factors.  With
         K None the draws come from the prior.  Returns (out (B, M, S), tries, fallback, jitter)."""
-        arr = progs if isinstance(progs, C.Array) else (_lib.KernelProg * len(progs))(*progs)
+        arr = self._progs(progs)
         B, args, res, keep = self._draws_args(Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm, Lp, maxtries)
         if len(arr) != B:
             raise G3Error('gp_draws_batched: %d programs for %d members' % (len(arr), B))
@@ -414,41 +418,32 @@ class Device:
                                 maxtries=20):
         """gp_draws_batched for members given as template + fields (see compile_spec_rows), after
         gp_factor_batched_fields on the same buffers"""
-        fields = np.ascontiguousarray(fields, dtype=np.float64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        nf = fields.shape[1]
-        if len(offsets) != nf:
-            raise G3Error('gp_draws_batched_fields: %d offsets for %d fields' % (len(offsets), nf))
+        rows, members = self._fields_args('gp_draws_batched_fields', tmpl, offsets, fields)
         B, args, res, keep = self._draws_args(Xs, M, X, N, d, K, kstride, W, a, lift, loc, Z, Cm, Lp, maxtries)
-        if fields.shape[0] != B:
-            raise G3Error('gp_draws_batched_fields: %d field rows for %d members' % (fields.shape[0], B))
-        rc = self.lib.g3_gp_draws_batched_fields(self.ctx, C.byref(tmpl), B, fields.ctypes.data, offsets.ctypes.data, nf, *args)
-        _check(self, rc, 'g3_gp_draws_batched_fields')
+        if rows != B:
+            raise G3Error('gp_draws_batched_fields: %d field rows for %d members' % (rows, B))
+        _check(self, self.lib.g3_gp_draws_batched_fields(self.ctx, *members, *args), 'g3_gp_draws_batched_fields')
         return res[0], res[1], res[2].astype(bool), res[3]
+
+    @staticmethod
+    def _dlogp_args(B, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha):
+        out = np.empty((B, max(gmap.nslots, 1)))
+        return out, (C.byref(gmap), X.ptr, N, X.ld, d, K.ptr, K.ld, kstride, W.ptr, a.ptr, _lib.dtype_code(K.dtype), Y.ptr,
+                     Kinv.ptr, alpha.ptr, out.ctypes.data_as(C.POINTER(C.c_double)))
 
     def gp_dlogp_batched(self, progs, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha):
         """after gp_factor_batched: per member K^-1, alpha and the kernel-parameter sums; returns (B, nslots)"""
-        B = len(progs)
-        arr = (_lib.KernelProg * B)(*progs)
-        out = (C.c_double * (max(gmap.nslots, 1) * B))()
-        rc = self.lib.g3_gp_dlogp_batched(self.ctx, arr, B, C.byref(gmap), X.ptr, N, X.ld, d, K.ptr, K.ld, kstride,
-                                          W.ptr, a.ptr, _lib.dtype_code(K.dtype), Y.ptr, Kinv.ptr, alpha.ptr, out)
-        _check(self, rc, 'g3_gp_dlogp_batched')
-        return np.array(out[:]).reshape(B, max(gmap.nslots, 1))[:, :gmap.nslots]
+        arr = self._progs(progs)
+        out, args = self._dlogp_args(len(arr), gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha)
+        _check(self, self.lib.g3_gp_dlogp_batched(self.ctx, arr, len(arr), *args), 'g3_gp_dlogp_batched')
+        return out[:, :gmap.nslots]
 
     def gp_dlogp_batched_fields(self, tmpl, offsets, fields, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha):
         """gp_dlogp_batched for members given as template + fields (after gp_factor_batched_fields on the same buffers);
         returns (B, nslots)"""
-        fields = np.ascontiguousarray(fields, dtype=np.float64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        B, nf = fields.shape
-        ns = max(gmap.nslots, 1)
-        out = np.empty((B, ns))
-        rc = self.lib.g3_gp_dlogp_batched_fields(self.ctx, C.byref(tmpl), B, fields.ctypes.data, offsets.ctypes.data, nf,
-                                                 C.byref(gmap), X.ptr, N, X.ld, d, K.ptr, K.ld, kstride, W.ptr, a.ptr,
-                                                 _lib.dtype_code(K.dtype), Y.ptr, Kinv.ptr, alpha.ptr,
-                                                 out.ctypes.data_as(C.POINTER(C.c_double)))
-        _check(self, rc, 'g3_gp_dlogp_batched_fields')
+        B, members = self._fields_args('gp_dlogp_batched_fields', tmpl, offsets, fields)
+        out, args = self._dlogp_args(B, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha)
+        _check(self, self.lib.g3_gp_dlogp_batched_fields(self.ctx, *members, *args), 'g3_gp_dlogp_batched_fields')
         return out[:, :gmap.nslots]
 
     def gp_sample(self, L, M, loc, Z):

@@ -220,6 +220,28 @@ class GaussianProcess(EllipticalProcess):
         self._chain_ws = ws
         return ws
 
+    def _chain_setup(self, n_rows, batch, default_batch, inputs=None, outputs=None, grad=False, pred=0, observed=True):
+        """what the block loops over a chain start from: (X, y, N, d, Np, kstride, batch, Xd, ws) with `batch` clamped to the
+        rows and the library's limit (None: the caller's default_batch(Np, kstride) -- how many members fit differs per
+        call), X uploaded once for the whole call and the workspace for `batch` members.  observed=False (a prior): no
+        device side, Xd and ws are None."""
+        X = self._x(self.inputs if inputs is None else inputs)
+        y = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
+        N, d = X.shape
+        Np = _lib.roundup(N)
+        kstride = (Np + _lib.G3_RHS_PAD) * Np
+        if batch is None:
+            batch = default_batch(Np, kstride)
+        batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
+        if not observed:
+            return X, y, N, d, Np, kstride, batch, None, None
+        return X, y, N, d, Np, kstride, batch, self.device.upload(X), self._chain_workspace(batch, Np, grad, pred=pred)
+
+    def _chain_members(self, kern, values_b, d, B):
+        """the members of `kern` for B chain rows as (template, offsets, fields) -- one program plus the hyper values that
+        differ per row (compile_spec_rows)"""
+        return compile_spec_rows(kern.spec(values_b, d), kern.spec(self._values_row(values_b, 0), d), d, B)
+
     # ---- posterior prediction over a chain (models.py:489-519: a loop of single predictions in the reference)
     _CHAIN_PREDICT = True
 
@@ -238,13 +260,12 @@ class GaussianProcess(EllipticalProcess):
         B, d = len(rows_b), S.shape[1]
         big = self.dtype.type(np.float32(1e10))
         values_b, _ = self._values_rows(rows_b)
-        values0 = self._values_row(values_b, 0)
-        members = compile_spec_rows(kern.spec(values_b, d), kern.spec(values0, d), d, B)
+        members = self._chain_members(kern, values_b, d, B)
         with np.errstate(all='ignore'):
             loc = np.asarray(self.f_location.rows(S, values_b, B), dtype=self.dtype)
         if prior:
             return values_b, members, loc, None, None
-        obs = compile_spec_rows(self.f_kernel_noise.spec(values_b, d), self.f_kernel_noise.spec(values0, d), d, B)
+        obs = self._chain_members(self.f_kernel_noise, values_b, d, B)
         with np.errstate(all='ignore'):
             mapped = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
             mapped = np.where(np.isnan(mapped), 0, np.where(np.isinf(mapped), big, mapped))
@@ -252,10 +273,25 @@ class GaussianProcess(EllipticalProcess):
         delta = np.where(np.isfinite(delta), delta, 0).astype(self.dtype)
         return values_b, members, loc, obs, delta
 
+    def _chain_delta_or_bad(self, values_b, X, y, B):
+        """the logp / dlogp rows' (delta, logdet_dinv, bad): a row with a non-finite entry takes the constant -1e30 branch
+        (gaussian.py:234-235); it is evaluated like the others on zeros, and its result replaced by the caller"""
+        with np.errstate(all='ignore'):
+            delta = (np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
+                     - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype))
+            det_m = np.asarray(self.f_mapping.logdet_dinv_rows(y, values_b, B), dtype=self.dtype)
+        bad = ~(np.isfinite(delta).all(axis=1) & np.isfinite(det_m))
+        if bad.any():
+            delta = np.where(bad[:, None], self.dtype.type(0), delta)
+        return delta, det_m, bad
+
     def _chain_factor_block(self, obs, delta, Xd, N, d, K, kstride, W, a):
-        """ONE batched factorisation of a block's observation covariances (g3_gp_factor_batched_fields)"""
+        """ONE batched factorisation of a block's observation covariances (g3_gp_factor_batched_fields).  `delta` comes
+        prepared by the caller, and not in one way: the logp / dlogp rows send a row with a non-finite entry as zeros and
+        replace its result by the constant -1e30 branch (gaussian.py:234-237, no scrub), the predict / sample rows scrub as
+        _factor / _solve('post') do for one row -- two behaviours of the reference, kept apart."""
         dev = self.device
-        dd = dev.upload(np.ascontiguousarray(delta))
+        dd = dev.upload(np.ascontiguousarray(delta, dtype=self.dtype))
         try:
             return dev.gp_factor_batched_fields(obs[0], obs[1], obs[2], Xd, N, d, dd, K, kstride, W, a)
         finally:
@@ -271,30 +307,25 @@ class GaussianProcess(EllipticalProcess):
         t = self.dtype.type
         big = t(np.float32(1e10))
         S = self._x(self.space if space is None else space)
-        X = self._x(self.inputs if inputs is None else inputs)
-        y = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
         n_rows, M = len(rows), S.shape[0]
-        N, d = X.shape
-        Np, Mp = _lib.roundup(N), _lib.roundup(M, _lib.G3_RHS_PAD)
+        Mp = _lib.roundup(M, _lib.G3_RHS_PAD)
         need_loc = switches['mean'] or switches['median'] or switches['quantiles']
         need_var = switches['var'] or switches['std'] or switches['quantiles']
         keys = self._predict_chain_keys(switches)
         out = DictObj((k, np.empty((n_rows, M), dtype=self.dtype)) for k in keys)
-        kstride = (Np + _lib.G3_RHS_PAD) * Np
-        if batch is None:
+
+        def fit(Np, kstride):
             # per member: factor + right-hand-side block, block inverses, a, and the three result vectors; the cross-Gram
             # blocks live in the library's own workspace (at most 256 MB of it, g3_gp_cross_batched)
             per = (3 * Mp if prior else kstride + Np * _lib.G3_PAD + Np + 3 * Mp) * self.dtype.itemsize
-            batch = int((4e9 - 2 ** 28) // per)
-        batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
+            return int((4e9 - 2 ** 28) // per)
         Sd = dev.upload(S)
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(n_rows, batch, fit, inputs, outputs, pred=Mp, observed=not prior)
         kern_c = self.f_kernel_noise if noise else self.f_kernel         # elliptical.py:78-79
         if prior:
             Xd, K, W, a, mu, ss = Sd, None, None, None, None, None
             kd = dev.alloc(batch, Mp, self.dtype) if need_var else None
         else:
-            Xd = dev.upload(X)
-            ws = self._chain_workspace(batch, Np, False, pred=Mp)
             K, W, a = ws['K'], ws['W'], ws['a']
             # the library writes the members' results roundup(M, 128) apart: views of that shape on the (wider) buffers
             mu, ss, kd = (dev.wrap(ws[k].ptr, batch, Mp, Mp, self.dtype, keep=ws[k]) for k in ('mu', 'ss', 'kd'))
@@ -363,16 +394,10 @@ class GaussianProcess(EllipticalProcess):
             N, d, K, W, a, kstride = 0, S.shape[1], None, None, None, 0
             batch = max(1, min(int(batch or _lib.G3_MAX_BATCH), n_rows, _lib.G3_MAX_BATCH))
         else:
-            X = self._x(self.inputs if inputs is None else inputs)
-            y = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
-            N, d = X.shape
-            Np = _lib.roundup(N)
-            kstride = (Np + _lib.G3_RHS_PAD) * Np
-            if batch is None:     # per member: factor + right-hand-side block, block inverses, a (V, C and Lp live in the library)
-                batch = int((4e9 - 2 ** 28) // ((kstride + Np * _lib.G3_PAD + Np) * self.dtype.itemsize))
-            batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
-            Xd = dev.upload(X)
-            ws = self._chain_workspace(batch, Np, False)
+            # per member: factor + right-hand-side block, block inverses, a (V, C and Lp live in the library)
+            X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+                n_rows, batch, lambda Np, kstride: int((4e9 - 2 ** 28) // ((kstride + Np * _lib.G3_PAD + Np) * self.dtype.itemsize)),
+                inputs, outputs)
             K, W, a = ws['K'], ws['W'], ws['a']
         try:
             for lo in range(0, n_rows, batch):
@@ -406,18 +431,9 @@ class GaussianProcess(EllipticalProcess):
                 out[i] = self.dlogp(chain[i], array=True)
             return out
         dev = self.device
-        X = self._x(self.inputs)
-        y = np.asarray(self.outputs, dtype=self.dtype).reshape(-1)
-        N, d = X.shape
-        Np = _lib.roundup(N)
-        kstride = (Np + _lib.G3_RHS_PAD) * Np
-        if batch is None:
-            batch = int(4e9 // (3 * kstride * self.dtype.itemsize))
-        batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
-        Xd = dev.upload(X)
-        ws = self._chain_workspace(batch, Np, True)
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+            n_rows, batch, lambda Np, kstride: int(4e9 // (3 * kstride * self.dtype.itemsize)), grad=True)
         K, Y, Ki, W, a, al = ws['K'], ws['Y'], ws['Ki'], ws['W'], ws['a'], ws['al']
-        t = self.dtype.type
         for lo in range(0, n_rows, batch):
             hi = min(lo + batch, n_rows)
             B = hi - lo
@@ -425,17 +441,9 @@ class GaussianProcess(EllipticalProcess):
             # warped observations, mean; the device then does factor, K^-1, alpha and the kernel-parameter sums of every
             # member in batched launches, and the chain rule below is array arithmetic over the rows
             values_b, _ = self._values_rows(chain[lo:hi])
-            tmpl, offs, fields = compile_spec_rows(self.f_kernel_noise.spec(values_b, d),
-                                                   self.f_kernel_noise.spec(self._values_row(values_b, 0), d), d, B)
-            with np.errstate(all='ignore'):
-                delta = (np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
-                         - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype))
-                det_m = np.asarray(self.f_mapping.logdet_dinv_rows(y, values_b, B), dtype=self.dtype)
-            bad = ~(np.isfinite(delta).all(axis=1) & np.isfinite(det_m))                  # constant -1e30 branch
-            if bad.any():
-                delta = np.where(bad[:, None], t(0), delta)
-            st = dev.gp_factor_batched_fields(tmpl, offs, fields, Xd, N, d, dev.upload(np.ascontiguousarray(delta, dtype=self.dtype)),
-                                              K, kstride, W, a)
+            tmpl, offs, fields = members = self._chain_members(self.f_kernel_noise, values_b, d, B)
+            delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
+            st = self._chain_factor_block(members, delta, Xd, N, d, K, kstride, W, a)
             gmap = dev.grad_layout(tmpl)
             ok = ~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0)
             nat = self._potential_gradient_rows(values_b, B)
@@ -528,17 +536,8 @@ class GaussianProcess(EllipticalProcess):
             if n_rows:                      # the free variables' terms only (th_logp with prior=True): no device work
                 out[:] = self._values_rows(chain)[1].astype(self.dtype)
             return out
-        dev = self.device
-        X = self._x(self.inputs)
-        y = np.asarray(self.outputs, dtype=self.dtype).reshape(-1)
-        N, d = X.shape
-        Np = _lib.roundup(N)
-        kstride = (Np + _lib.G3_RHS_PAD) * Np
-        if batch is None:
-            batch = int(4e9 // (kstride * self.dtype.itemsize))
-        batch = max(1, min(int(batch), n_rows, _lib.G3_MAX_BATCH))
-        Xd = dev.upload(X)
-        ws = self._chain_workspace(batch, Np, False)
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+            n_rows, batch, lambda Np, kstride: int(4e9 // (kstride * self.dtype.itemsize)))
         K, W, a = ws['K'], ws['W'], ws['a']
         for lo in range(0, n_rows, batch):
             hi = min(lo + batch, n_rows)
@@ -546,18 +545,8 @@ class GaussianProcess(EllipticalProcess):
             # the whole block at once on the host: values, programs (one template + the hyper values that differ per
             # row), warped observations and the mean -- O(B) NumPy passes, no per-row Python
             values_b, logjac = self._values_rows(chain[lo:hi])
-            values0 = self._values_row(values_b, 0)
-            tmpl, offs, fields = compile_spec_rows(self.f_kernel_noise.spec(values_b, d),
-                                                   self.f_kernel_noise.spec(values0, d), d, B)
-            with np.errstate(all='ignore'):
-                delta = (np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
-                         - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype))
-                det_m = np.asarray(self.f_mapping.logdet_dinv_rows(y, values_b, B), dtype=self.dtype)
-            bad = ~(np.isfinite(delta).all(axis=1) & np.isfinite(det_m))                  # gaussian.py:234-235
-            if bad.any():
-                delta = np.where(bad[:, None], t(0), delta)        # evaluated like the others, result replaced below
-            dd = dev.upload(np.ascontiguousarray(delta, dtype=self.dtype))
-            st = dev.gp_factor_batched_fields(tmpl, offs, fields, Xd, N, d, dd, K, kstride, W, a)
+            delta, det_m, bad = self._chain_delta_or_bad(values_b, X, y, B)
+            st = self._chain_factor_block(self._chain_members(self.f_kernel_noise, values_b, d, B), delta, Xd, N, d, K, kstride, W, a)
             with np.errstate(all='ignore'):
                 lp = logjac.astype(self.dtype) + self._chain_density(values_b, st, det_m, N, B).astype(self.dtype)
             bad |= ~np.isfinite(st[:, 0]) | (st[:, 2] > 0)                                # gaussian.py:237

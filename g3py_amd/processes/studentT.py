@@ -65,6 +65,10 @@ class StudentTProcess(EllipticalProcess):
     logp_chain = GaussianProcess.logp_chain
     dlogp_chain = GaussianProcess.dlogp_chain
     _chain_workspace = GaussianProcess._chain_workspace
+    _chain_setup = GaussianProcess._chain_setup
+    _chain_members = GaussianProcess._chain_members
+    _chain_delta_or_bad = GaussianProcess._chain_delta_or_bad
+    _chain_factor_block = GaussianProcess._chain_factor_block
     _potential_gradient_rows = GaussianProcess._potential_gradient_rows
     _chain_rule_rows = GaussianProcess._chain_rule_rows
     _flat_gradient_rows = GaussianProcess._flat_gradient_rows

@@ -2,12 +2,14 @@
 // shim"): g3py_amd/csrc/g3_host.h is pure C++ and is compiled here with g++ -fsanitize=address,undefined.  Every
 // table / schedule builder is driven over the shapes the library produces (and some it never should) and its output
 // is checked the way the device consumes it: the tile lookup of the GEMM kernel, the op list of the stripe solve, the
-// chunking of the multi-GPU staircase, panel boundaries, the fast-path matcher, the program ring, the jitter schedule.
+// chunking of the multi-GPU staircase, panel boundaries, the fast-path matcher, the program ring, the jitter schedule, the layout
+// of the batched entry points' device buffer and the host expansion of a chain member.
 // TEST INFRASTRUCTURE: never linked into the product.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <random>
 #include <set>
@@ -373,6 +375,70 @@ static void test_dealing() {
     }
 }
 
+// the batched entry points' device buffer (g3h_member_layout) and the host expansion of a chain member (MemberProgs)
+static void test_member_layout() {
+  const size_t P = sizeof(g3_kernel_prog);
+  CHECK(P % 8 == 0);
+  for (int batch : {1, 2, 4096})
+    for (int nfield : {0, 1, 7, (int)G3_MAX_FIELDS})
+      for (int whole : {0, 1})
+        for (size_t stat : {(size_t)0, (size_t)batch * 32})
+          for (size_t tail : {(size_t)0, (size_t)1000}) {
+            const G3hMemberLayout lo = g3h_member_layout(batch, nfield, whole, stat, tail);
+            const size_t fbytes = whole ? 0 : (size_t)batch * nfield * 8, obytes = whole ? 0 : ((size_t)nfield * 4 + 15) / 16 * 16;
+            // ordered, disjoint: every region ends where the next begins or before it
+            CHECK(lo.progs == 0 && lo.progs + batch * P <= lo.stats && lo.stats + stat <= lo.tmpl);
+            CHECK(lo.tmpl + (whole ? 0 : P) <= lo.fields && lo.fields + fbytes <= lo.offs && lo.offs + obytes <= lo.tail);
+            CHECK(lo.stats % 8 == 0 && lo.tmpl % 8 == 0 && lo.fields % 8 == 0 && lo.offs % 4 == 0);
+            CHECK(lo.tail % 256 == 0 && lo.tail - (lo.offs + obytes) < 256 && lo.total == lo.tail + tail);
+            // the closed forms the three callers wrote out by hand: programs, [statistics], [template, fields, offsets table]
+            CHECK(lo.stats == batch * P && lo.tmpl == batch * P + stat);
+            CHECK(lo.fields == lo.tmpl + (whole ? 0 : P) && lo.offs == lo.fields + fbytes);
+            CHECK(lo.tail == ((batch * P + stat + (whole ? 0 : P) + fbytes + obytes + 255) & ~(size_t)255));
+          }
+  // member(b) of the template form == the template patched by hand; of the whole form == the program itself
+  std::mt19937 rng(13);
+  g3_kernel_prog tmpl;
+  memset(&tmpl, 0, sizeof(tmpl));
+  tmpl.nleaf = G3_MAXLEAF;
+  tmpl.nprod = G3_MAXPROD;
+  tmpl.leaf[1].kind = G3_K_DOT;          // its exponent (freq[0]) is structure: never a valid field
+  std::vector<int32_t> valid;
+  for (int32_t off = -8; off < (int32_t)P + 16; off += 4)
+    if (g3h_field_offset_ok_tmpl(&tmpl, off)) valid.push_back(off);
+  CHECK(!valid.empty() && valid.size() <= (size_t)G3_MAX_FIELDS);
+  CHECK(!g3h_field_offset_ok_tmpl(&tmpl, (int32_t)((char*)&tmpl.leaf[1].freq[0] - (char*)&tmpl)));
+  for (int nfield : {0, 1, 7, (int)valid.size()})
+    for (int batch : {1, 2, 5}) {
+      std::vector<int32_t> offs(valid);
+      std::shuffle(offs.begin(), offs.end(), rng);
+      offs.resize(nfield);                 // distinct valid offsets, exactly nfield of them (no slack behind the arrays)
+      std::vector<double> fields((size_t)batch * nfield);
+      for (auto& v : fields) v = (double)(rng() % 1000) + 0.5;
+      MemberProgs mp;
+      mp.tmpl = &tmpl;
+      mp.fields = fields.data();
+      mp.offs = offs.data();
+      mp.nfield = nfield;
+      std::vector<g3_kernel_prog> whole((size_t)batch);
+      for (int b = 0; b < batch; ++b) {
+        g3_kernel_prog want = tmpl, got;
+        memset(&got, 0xCD, sizeof(got));
+        for (int i = 0; i < nfield; ++i) *(double*)((char*)&want + offs[i]) = fields[(size_t)b * nfield + i];
+        mp.member(b, &got);
+        CHECK(!memcmp(&got, &want, sizeof(got)));
+        whole[b] = want;
+      }
+      MemberProgs mw;
+      mw.progs = whole.data();
+      for (int b = 0; b < batch; ++b) {
+        g3_kernel_prog got;
+        mw.member(b, &got);
+        CHECK(!memcmp(&got, &whole[b], sizeof(got)));
+      }
+    }
+}
+
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "deal")) {        // "deal P nblk": print the table (the Python twin must deal identically)
     std::vector<int> owner;
@@ -387,6 +453,7 @@ int main(int argc, char** argv) {
   test_panel_bounds();
   test_match_and_validate();
   test_ring_and_jitter();
+  test_member_layout();
   if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }
   printf("host_asan ok\n");
   return 0;
