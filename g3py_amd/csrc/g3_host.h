@@ -24,6 +24,18 @@ static inline int g3h_env_int(const char* name, int dflt) {
 // travel with the context: no launch path looks at the environment, so contexts on different threads never race on a
 // lazily initialised static (include/g3hip.h: distinct contexts may run concurrently).  Defaults are what was measured
 // on MI355X; every knob selects another schedule of the SAME arithmetic.
+//
+// G3_GEMM_LOG=<file> (also read when the context is created; the file is opened for appending and flushed when the context is
+// destroyed) records which variant every launch took, one line of eleven space-separated fields per launch, in launch order.
+// tests/test_gpu_kernel_variants.py parses it, so the format is part of what the tests pin:
+//   gemm BM BN waves m n k kind ntiles flops bulk     one gemm_nt_kernel<T, BM, BN, ...> launch (g3_gemm.hip::launch_cfg)
+//   trsm BM 128 4 m n n 0 nstripes flops bulk         one trsm_stripe_kernel<T, BM> launch (g3_gemm.hip::trsm_stripe_t)
+// BM x BN: the tile (64 x 64, 128 x 128, or 32 x 128 for the in-place leaf product), waves: per workgroup (4 / 8 / 4); the
+// stripe solve writes its stripe height BM, the 128 columns of its tiles and its 4 waves in the same places.  m, n, k: the
+// extent of C and the reduction length (stripe solve: m panel rows against an n x n triangle); kind: GemmShape::kind (0 dense,
+// 1 trapezoid, 2 staircase); ntiles: workgroups in grid.x (tiles launched; nstripes = m / BM); flops: the algorithmic count
+// (%.9e); bulk: 1 when the launch went to the low-priority side stream of a two-stream sweep, else 0.  A batched sweep's
+// members are grid.y of the same launch: one line.
 struct G3hTune {
   int64_t nb;             // G3_NB          panel width of the look-ahead sweeps (0: by matrix size)
   int sb;                 // G3_SB          panels per super-panel (1)
