@@ -557,8 +557,12 @@ def compile_spec(spec, d):
         kind = lf[0]
         L.kind = _lib.KINDS[kind]
         L.var = float(lf[1])
-        dims = lf[-1] if kind not in ('NOISE', 'VAR') else None
-        dims = np.arange(d) if dims is None else np.atleast_1d(np.asarray(dims)).astype(int)
+        if kind in ('NOISE', 'VAR'):
+            # these read no column: the index list they carry is cut at what a leaf holds, or an input of more than
+            # G3_MAXD columns could have no noise term
+            dims = np.arange(min(d, _lib.G3_MAXD))
+        else:
+            dims = np.arange(d) if lf[-1] is None else np.atleast_1d(np.asarray(lf[-1])).astype(int)
         dims = np.where(dims < 0, dims + d, dims)
         if len(dims) > _lib.G3_MAXD or (len(dims) and (dims.min() < 0 or dims.max() >= d)):
             raise G3Error('bad dims for kernel leaf %s' % kind)

@@ -291,3 +291,51 @@ def test_chain_rows_packing_equals_row_by_row():
                 np.testing.assert_array_equal(inv_b[j], np.asarray(gp.f_mapping.inv(yv, values), dtype=gp.dtype))
                 np.testing.assert_array_equal(loc_b[j], gp.f_location(X, values))
                 assert np.array_equal(det_b[j], gp.dtype.type(gp.f_mapping.logdet_dinv(yv, values)), equal_nan=True)
+
+
+def test_generated_kernels_compile_for_wide_inputs():
+    """the kernels generated for inputs of 16, 32 and 40 columns (tests/wide_reference.py: leaves on up to 32 columns, column
+    subsets, descending dims, the trig-pair boundary cases) compile for gfx950 on the build host, fp64 and fp32: every
+    structure the library hands to hipRTC -- at most 24 trig pairs for the Gram kernel (g3i_gram_jit), at most
+    G3_GRAD_JIT_MAXSLOTS = 40 register accumulators for the gradient kernel (g3i_grad_jit_function) -- gives a code object"""
+    import ctypes as C
+    from g3py_amd import _lib
+    from g3py_amd.device import compile_spec
+    import wide_reference as wr
+    lib = _lib.load()
+    gram = [('%s d=%d' % (name, d), d, spec) for d in (16, 32, 40) for name, spec in wr.width_specs(d).items()]
+    gram += [(name, d, spec) for name, (d, spec, pairs) in wr.boundary_cases().items() if pairs <= wr.JIT_MAX_PAIRS]
+    # (the five stationary kinds on all 16 columns are on the gradient's compile-time table: nothing is generated for them)
+    grad = gram[:9] + [(name, d, spec) for name, (d, spec, slots) in wr.gradient_specs().items() if not name.startswith('d16_')]
+    assert {d for _, d, _ in gram} == {16, 32, 40} and {d for _, d, _ in grad} >= {16, 31, 32, 38, 40}
+    done = {'gram': 0, 'grad': 0, 'grad40': 0}
+    for which, cases, check in (('gram', gram, lib.g3_gram_jit_check), ('grad', grad, lib.g3_grad_jit_check)):
+        for name, d, spec in cases:
+            prog = compile_spec(spec, d)
+            if which == 'grad':
+                gmap = _lib.GradMap()
+                assert lib.g3_grad_layout(C.byref(prog), C.byref(gmap)) == 0
+                if gmap.nslots > 40:
+                    continue                  # the library interprets these (G3_GRAD_JIT_MAXSLOTS)
+                done['grad40'] += gmap.nslots == 40
+            for dt in (0, 1):
+                cb, log = C.c_int64(0), C.create_string_buffer(8000)
+                rc = check(C.byref(prog), d, dt, C.byref(cb), log, 8000)
+                if rc == -1:
+                    pytest.skip('libhiprtc is not available on this host')
+                assert rc == 0 and cb.value > 1000, (which, name, d, dt, rc, log.value.decode()[:3000])
+                done[which] += 1
+    assert done['gram'] == 2 * len(gram) and done['grad'] >= 20 and done['grad40'] >= 1, done
+
+
+def test_noise_term_lowers_on_inputs_wider_than_one_leaf():
+    """a NOISE leaf reads no column, so it lowers at every input width up to G3_MAXCOLS = 40 (a leaf holds 32 column
+    indices); the lowered program is the oracle's expression, square (noise on the diagonal) and cross (none)"""
+    import wide_reference as wr
+    for d in (32, 33, 40):
+        spec = orc.with_noise(wr.se_plus_cos(d, 12), 0.1)
+        prog = compile_spec(spec, d)
+        assert prog.nleaf == 3 and max(prog.leaf[i].ndims for i in range(3)) <= 32
+        X, X2 = wr.inputs(40, d), wr.inputs(11, d, seed=1)
+        np.testing.assert_allclose(_eval_prog(prog, X), orc.kernel_cov(spec, X), rtol=1e-13)
+        np.testing.assert_allclose(_eval_prog(prog, X2, X), orc.kernel_cov(spec, X2, X), rtol=1e-13)
