@@ -92,6 +92,22 @@ int g3i_ensure_side_stream(g3_ctx* ctx) {
   return G3_OK;
 }
 
+// The event pool of the two-stream sweeps.  la_nev counts the events that exist, whichever way out is taken:
+// g3_ctx_destroy walks them.
+int g3i_ensure_events(g3_ctx* ctx, int need) {
+  if (ctx->la_nev >= need) return G3_OK;
+  if (ctx->in_sweep) {
+    snprintf(ctx->err, sizeof(ctx->err), "the event pool cannot grow (%d -> %d) inside a two-stream sweep", ctx->la_nev, need);
+    return G3_ERR_HIP;
+  }
+  for (; ctx->la_nev > 0; --ctx->la_nev) (void)hipEventDestroy(ctx->la_ev[ctx->la_nev - 1]);
+  free(ctx->la_ev);
+  ctx->la_ev = (hipEvent_t*)calloc((size_t)need, sizeof(hipEvent_t));
+  if (!ctx->la_ev) return G3_ERR_NOMEM;
+  for (; ctx->la_nev < need; ++ctx->la_nev) G3_HIP(hipEventCreateWithFlags(&ctx->la_ev[ctx->la_nev], hipEventDisableTiming));
+  return G3_OK;
+}
+
 static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out) {
   if (!out) return -2;
   *out = nullptr;
@@ -118,12 +134,6 @@ static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out) {
     const char* lg = getenv("G3_GEMM_LOG");
     ctx->gemm_log = (lg && *lg) ? fopen(lg, "a") : nullptr;
   }
-#ifdef G3_CHAIN_SERVER   // measurement variant (scripts/variants/chain_server.inc): G3_CHAIN=1 puts the chain of a sweep on resident workgroups
-  ctx->chain_wgs = g3h_env_int("G3_CHAIN", 0) ? g3h_env_int("G3_CHAIN_WGS", 16) : 0;
-  ctx->chain_lds = g3h_env_int("G3_CHAIN_LDS", 0);
-  ctx->chain_min_n = g3h_env_int("G3_CHAIN_MIN_N", 0);
-  ctx->chain_max_n = g3h_env_int("G3_CHAIN_MAX_N", 10240);
-#endif
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_info, G3_MAX_BATCH * sizeof(int));
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_stats, 64 * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_prog, G3_PROG_SLOTS * sizeof(g3_kernel_prog));
@@ -169,16 +179,6 @@ extern "C" int g3_ctx_destroy(g3_ctx* ctx) {
     for (int i = 0; i < ctx->la_nev; ++i) (void)hipEventDestroy(ctx->la_ev[i]);
     free(ctx->la_ev);
   }
-#ifdef G3_CHAIN_SERVER
-  for (hipStream_t* st : {&ctx->chain_stream, &ctx->chain_stream2, &ctx->chain_sA, &ctx->chain_sB})
-    if (*st) {
-      (void)hipStreamSynchronize(*st);
-      (void)hipStreamDestroy(*st);
-    }
-  for (hipEvent_t* ev : {&ctx->chain_ev, &ctx->chain_ev2, &ctx->chain_ev3})
-    if (*ev) (void)hipEventDestroy(*ev);
-  if (ctx->chain_ctl) (void)hipFree(ctx->chain_ctl);
-#endif
   if (ctx->gemm_log) fclose(ctx->gemm_log);
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -630,17 +630,6 @@ extern "C" int g3_scrub(g3_ctx* ctx, void* A, int64_t n1, int64_t n2, int64_t ld
   return G3_OK;
 }
 
-static int logp_terms_launch(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, const void* a, g3_dtype dt) {
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((logp_terms_kernel<double>), dim3(1), dim3(1024), 0, ctx->stream, (const double*)L, n, ld,
-                       (const double*)a, ctx->d_stats, (int64_t)0, (int64_t)0);
-  else
-    hipLaunchKernelGGL((logp_terms_kernel<float>), dim3(1), dim3(1024), 0, ctx->stream, (const float*)L, n, ld,
-                       (const float*)a, ctx->d_stats, (int64_t)0, (int64_t)0);
-  G3_LAUNCH_CHECK();
-  return G3_OK;
-}
-
 int g3i_logp_terms_dev(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, const void* a, g3_dtype dt, double* out_dev) {
   if (dt == G3_F64)
     hipLaunchKernelGGL((logp_terms_kernel<double>), dim3(1), dim3(1024), 0, ctx->stream, (const double*)L, n, ld,
@@ -660,7 +649,7 @@ extern "C" int g3_logp_terms(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, 
   if (n <= 0) return -3;
   if (ld < n) return -4;
   if (!out) return -7;
-  int rc = logp_terms_launch(ctx, L, n, ld, a, dt);
+  int rc = g3i_logp_terms_dev(ctx, L, n, ld, a, dt, ctx->d_stats);
   if (rc) return rc;
   return fetch_stats(ctx, out, 4);
 }
@@ -791,21 +780,11 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
     if (r) return r;
     return build_rhs();
   };
-  auto factor = [&](int* info) -> int {
+  auto factor = [&]() -> int {
     const int pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)N * N * N / 3.0 + (double)N * N * (1 + M));
-    int r = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, E);
+    const int r = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, E);
     g3i_prof_end(ctx, pr);
-    if (r) return r;
-    G3_HIP(hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    G3_HIP(hipStreamSynchronize(ctx->stream));
-    *info = *ctx->h_info;
-#ifdef G3_CHAIN_SERVER
-    if (g3i_chain_gave_up(ctx, *info)) {   // (cannot happen twice: the server is off after the first time)
-      snprintf(ctx->err, sizeof(ctx->err), "chain server gave up inside a jitter retry");
-      return G3_ERR_HIP;
-    }
-#endif
-    return G3_OK;
+    return r;
   };
   // scalars of the evaluation: log-determinant, quadratic form, guards (and mean / sum of squares per query)
   double st4[5];
@@ -828,33 +807,13 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
   };
   rc = build();
   if (rc) return rc;
-  int info = 0;
-  {
-    // first attempt: the pivot flag comes back with the reductions -- one round trip per evaluation instead of two
-    // (the reductions of a failed factorisation are simply discarded)
-    const int pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)N * N * N / 3.0 + (double)N * N * (1 + M));
-    rc = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, E);
-    g3i_prof_end(ctx, pr);
-    if (rc) return rc;
-    rc = finish();
-    if (rc) return rc;
-    info = (int)st4[4];
-#ifdef G3_CHAIN_SERVER
-    if (g3i_chain_gave_up(ctx, info)) {
-      // the resident chain workgroups ran into their wall-clock limit (they are off from now on): this evaluation is
-      // redone with the launch-per-kernel sweep
-      rc = g3i_reset_info(ctx);
-      if (!rc) rc = build();
-      if (rc) return rc;
-      const int pr2 = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)N * N * N / 3.0 + (double)N * N * (1 + M));
-      rc = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, E);
-      g3i_prof_end(ctx, pr2);
-      if (!rc) rc = finish();
-      if (rc) return rc;
-      info = (int)st4[4];
-    }
-#endif
-  }
+  // first attempt: the pivot flag comes back with the reductions -- one round trip per evaluation instead of two
+  // (the reductions of a failed factorisation are simply discarded)
+  rc = factor();
+  if (rc) return rc;
+  rc = finish();
+  if (rc) return rc;
+  int info = (int)st4[4];
   double tries = 0, fallback = 0;
   const int info0 = info;
   if (info != 0) {
@@ -875,7 +834,8 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
       }
       rc = g3_diag_add(ctx, K, N, ldk, dt, jit.value());
       if (rc) return rc;
-      rc = factor(&info);
+      rc = factor();
+      if (!rc) rc = g3i_read_info(ctx, &info);
       if (rc) return rc;
       if (info == 0) { ok = true; break; }
       jit.next();

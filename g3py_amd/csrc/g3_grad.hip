@@ -24,21 +24,6 @@
 // ------------------------------------------------------------------------------------------
 // K^-1 from the factor
 // ------------------------------------------------------------------------------------------
-static int ensure_events(g3_ctx* ctx, int need) {
-  if (ctx->la_nev >= need) return G3_OK;
-  if (ctx->la_ev) {
-    for (int i = 0; i < ctx->la_nev; ++i) (void)hipEventDestroy(ctx->la_ev[i]);
-    free(ctx->la_ev);
-    ctx->la_ev = nullptr;
-    ctx->la_nev = 0;
-  }
-  ctx->la_ev = (hipEvent_t*)calloc((size_t)need, sizeof(hipEvent_t));
-  if (!ctx->la_ev) return G3_ERR_NOMEM;
-  for (int i = 0; i < need; ++i) G3_HIP(hipEventCreateWithFlags(&ctx->la_ev[i], hipEventDisableTiming));
-  ctx->la_nev = need;
-  return G3_OK;
-}
-
 // Y (n x n, upper triangular on return) = L^-T and C (lower triangle) = K^-1 = Y Y^T.
 // Right-looking over NB-wide panels of columns: panel k of Y is final after the solve against
 // L_kk; it then updates the columns to its right (rows 0..r1 only: Y is upper triangular, so
@@ -55,22 +40,21 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
               int64_t ldy, void* C, int64_t ldc) {
   if (n == 0) return G3_OK;
   const size_t es = g3_esize(dt);
-  int64_t NB = ctx->nb_lookahead;
-  if (NB <= 0) {
-    // the inverse's chain is light (one panel solve per step): wide panels from mid sizes on
-    // (measured, dlogp: N=8192 9.4 -> 8.4 ms, 16384 55.7 -> 55.0 ms)
-    NB = ctx->tune.nb > 0 ? ctx->tune.nb : (n <= 4096 ? 128 : (n <= 6144 ? 256 : (n <= 12288 ? 512 : 1024)));
-  }
+  // the inverse's chain is light (one panel solve per step): wide panels from mid sizes on
+  // (measured, dlogp: N=8192 9.4 -> 8.4 ms, 16384 55.7 -> 55.0 ms)
+  int64_t NB = ctx->tune.nb > 0 ? ctx->tune.nb : g3h_default_panel_width(n);
   NB = g3_roundup(NB < G3_LB ? G3_LB : NB, G3_LB);
   const int nblk = (int)((n + NB - 1) / NB);
-  int rc = ensure_events(ctx, 2 * nblk + 2);
+  int rc = g3i_ensure_events(ctx, 2 * nblk + 2);
   if (rc) return rc;
   hipEvent_t* evP = ctx->la_ev;
   hipEvent_t* evB = ctx->la_ev + nblk;
   const bool two = nblk >= 3;   // small problems: everything on the caller's stream
-  if (two) { const int rs = g3i_ensure_side_stream(ctx); if (rs) return rs; }
-  hipStream_t sA = ctx->stream, sB = ctx->side_stream;
-  if (!two) sB = sA;
+  if (two) {
+    rc = g3i_ensure_side_stream(ctx);
+    if (rc) return rc;
+  }
+  hipStream_t sA = ctx->stream, sB = two ? ctx->side_stream : sA;
 
   if (g3_nbatch(ctx) > 1 && ((n * es) % 16 == 0) && ((ldy * es) % 16 == 0) && ((ldc * es) % 16 == 0) &&
       ((((uintptr_t)Y | (uintptr_t)C) & 15) == 0) && ((g3_bstride_of(ctx, Y) * es) % 16 == 0) && ((g3_bstride_of(ctx, C) * es) % 16 == 0)) {
@@ -90,10 +74,8 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
   }
   rc = g3i_diag_add(ctx, Y, n, ldy, dt, 1.0);
   if (rc) return rc;
-  if (two) {
-    G3_HIP(hipEventRecord(evB[nblk], sA));
-    G3_HIP(hipStreamWaitEvent(sB, evB[nblk], 0));
-  }
+  g3_sweep_scope sweep(ctx, sB, evB[nblk]);   // (one-stream mode: sB == sA, no sweep)
+  if (sweep.rc) return sweep.rc;
   auto r = [&](int k) { return (int64_t)k * NB < n ? (int64_t)k * NB : n; };
   auto Lp = [&](int64_t i, int64_t j) { return (const char*)L + ((size_t)i * ldl + j) * es; };
   auto Yp = [&](int64_t j) { return (char*)Y + (size_t)j * es; };   // row 0, column j
@@ -117,17 +99,20 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
     const int64_t r2 = r(k + 2), r3 = r(k + 3);
     // bulk stream: columns beyond the next panel, then this panel's share of K^-1
     if (two) G3_HIP(hipStreamWaitEvent(sB, evP[k], 0));
-    ctx->stream = sB;
-    if (r2 < n) {
-      rc = update(k, r2, r3);
-      if (!rc && two && hipEventRecord(evB[k], sB) != hipSuccess) rc = G3_ERR_HIP;
-      if (!rc && r3 < n) rc = update(k, r3, n);
-    } else if (two && hipEventRecord(evB[k], sB) != hipSuccess) {
-      rc = G3_ERR_HIP;
+    {
+      g3_stream_scope on_bulk(ctx, sB);
+      if (r2 < n) {
+        rc = update(k, r2, r3);
+        if (rc) return rc;
+      }
+      if (two) G3_HIP(hipEventRecord(evB[k], sB));
+      if (r3 < n) {
+        rc = update(k, r3, n);
+        if (rc) return rc;
+      }
+      rc = syrk(k);
+      if (rc) return rc;
     }
-    if (!rc) rc = syrk(k);
-    ctx->stream = sA;
-    if (rc) return rc;
     // critical path: next panel
     if (two && k >= 1) G3_HIP(hipStreamWaitEvent(sA, evB[k - 1], 0));
     rc = update(k, r(k + 1), r2);
@@ -137,15 +122,12 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
     if (two) G3_HIP(hipEventRecord(evP[k + 1], sA));
   }
   if (two) G3_HIP(hipStreamWaitEvent(sB, evP[nblk - 1], 0));
-  ctx->stream = sB;
-  rc = syrk(nblk - 1);
-  ctx->stream = sA;
-  if (rc) return rc;
-  if (two) {
-    G3_HIP(hipEventRecord(evB[nblk], sB));
-    G3_HIP(hipStreamWaitEvent(sA, evB[nblk], 0));
+  {
+    g3_stream_scope on_bulk(ctx, sB);
+    rc = syrk(nblk - 1);
+    if (rc) return rc;
   }
-  return G3_OK;
+  return sweep.join();
 }
 
 extern "C" int g3_potri(g3_ctx* ctx, const void* L_dev, int64_t n, int64_t ldl, const void* invd_dev, g3_dtype dt,

@@ -292,12 +292,22 @@ struct TrsmOps {
 };
 
 
-static inline int64_t trsm_split(int64_t n) {     // must mirror split_point() of g3_potrf.hip (same recursion shape)
+// Where the recursions over 128-wide blocks split n columns (n a multiple of 128 and > 128) into n1 + (n - n1): near the
+// middle, on a coarse power-of-two grid so that large sub-problems keep tile-friendly sizes.  The factorisation, the
+// launch-level solve (g3_potrf.hip) and the op list of the one-launch stripe solve below all split here.
+static inline int64_t g3h_split_point(int64_t n) {
   int64_t g = G3H_LB;
   while (g * 2 <= n / 4 && g < 2048) g *= 2;
   int64_t n1 = g3h_roundup(n / 2, g);
   if (n1 >= n) n1 = n - G3H_LB;
   return n1;
+}
+
+// Default panel width of the look-ahead sweeps by matrix size (G3_NB overrides it).  Measured on MI355X (fp64): narrow
+// panels shorten the latency-bound chain of diagonal-block kernels that dominates small problems, wide panels give the
+// bulk updates more K.
+static inline int64_t g3h_default_panel_width(int64_t n) {
+  return n <= 4096 ? 128 : (n <= 6144 ? 256 : (n <= 12288 ? 512 : 1024));
 }
 
 static inline void trsm_ops_rec(TrsmOps* ops, int64_t c0, int64_t n) {
@@ -306,7 +316,7 @@ static inline void trsm_ops_rec(TrsmOps* ops, int64_t c0, int64_t n) {
     o.col = (int)c0; o.acol = (int)c0; o.k = G3H_LB; o.brow = (int)(c0 / G3H_LB); o.bcol = 0; o.leaf = 1;
     return;
   }
-  const int64_t n1 = trsm_split(n), n2 = n - n1;
+  const int64_t n1 = g3h_split_point(n), n2 = n - n1;
   trsm_ops_rec(ops, c0, n1);
   for (int64_t t = 0; t < n2; t += G3H_LB) {       // X[:, c0+n1+t .. +128) -= X[:, c0 .. c0+n1) L[c0+n1+t .., c0 ..)^T
     auto& o = ops->op[ops->nops++];

@@ -17,9 +17,9 @@ struct g3_ctx {
   hipStream_t own_stream;  // created by the context
   hipStream_t side_stream; // low-priority stream carrying the bulk trailing updates (look-ahead)
   hipStream_t side_for;    // the stream the side stream's placement was probed against (g3i_ensure_side_stream)
-  hipEvent_t* la_ev;       // look-ahead events (2 per panel)
+  hipEvent_t* la_ev;       // event pool of the two-stream sweeps (g3i_ensure_events)
   int la_nev;
-  int64_t nb_lookahead;    // panel width of the flat right-looking sweep (0 = default)
+  bool in_sweep;           // a two-stream sweep owns the side stream and the event pool (g3_sweep_scope)
   G3hTune tune;            // tuning knobs, read from the environment once at g3_ctx_create
   unsigned long long gram_paths[3];   // Gram launches so far: compile-time table, generated at first use, interpreted
   unsigned long long grad_paths[3];   // the same for the gradient's kernel-parameter sums
@@ -28,19 +28,8 @@ struct g3_ctx {
                            // info_sync), or cleared on info_stream with no factorisation queued since (g3i_reset_info)
   bool info_sync;
   hipStream_t info_stream;
-  bool fuse256;            // factor 256-wide diagonal blocks with the one-launch kernel (chain-bound sizes)
   bool adopted;            // stream belongs to the caller
   bool bulk_role;          // this context's stream carries bulk updates beside another context's chain (multi-GPU driver)
-#ifdef G3_CHAIN_SERVER   // measurement variant only (scripts/variants/chain_server.inc): the chain of a sweep on resident workgroups
-  unsigned* chain_ctl;     // device: counters and per-panel flags of the running server
-  hipStream_t chain_sA, chain_sB;            // the chain sweep's own chain / bulk streams (created with the two below)
-  hipStream_t chain_stream, chain_stream2;   // streams of the server's two kernels (diagonal workgroup, workers)
-  hipEvent_t chain_ev, chain_ev2, chain_ev3; // bracket of the caller's stream, end of the two server kernels
-  int chain_wgs;           // workgroups of the server (< 2: off)
-  int chain_lds;           // LDS bytes a server workgroup asks for (0: what it needs)
-  int64_t chain_min_n, chain_max_n;   // matrices the server is used for
-  bool chain_broken;       // a server gave up (wall-clock limit): launches per kernel from then on
-#endif
   // batch mode (g3_gp_factor_batched): every MFMA GEMM and diagonal-block launch of a sweep acts on
   // `batch` matrices at once (grid.y); operands inside the block-inverse buffer [bw_base, +bw_bytes)
   // are `bstride_w` elements apart, everything else `bstride` elements
@@ -153,12 +142,54 @@ struct g3_batch_scope {
 };
 
 // launches issued now go to the low-priority bulk stream of the look-ahead sweep
-static inline bool g3_on_bulk_stream(const g3_ctx* ctx) {
-#ifdef G3_CHAIN_SERVER
-  if (ctx->chain_sB && ctx->stream == ctx->chain_sB) return true;
-#endif
-  return ctx->stream == ctx->side_stream;
-}
+static inline bool g3_on_bulk_stream(const g3_ctx* ctx) { return ctx->stream == ctx->side_stream; }
+
+// ---- scaffold of the two-stream sweeps (potrf_lookahead and trsm_lookahead in g3_potrf.hip, g3i_potri in g3_grad.hip)
+// The context's event pool holds at least `need` events.  Growing it destroys the events it held, so it is refused while a
+// sweep is active: the sweep's event pointers would dangle.
+int g3i_ensure_events(g3_ctx* ctx, int need);
+
+// Launches issued while the object lives go to stream `s` (a sweep's bulk stream).  Every way out of the scope, the early
+// return of G3_HIP included, puts the context back on the stream it was on.
+struct g3_stream_scope {
+  g3_ctx* ctx;
+  hipStream_t prev;
+  g3_stream_scope(g3_ctx* c, hipStream_t s) : ctx(c), prev(c->stream) { ctx->stream = s; }
+  ~g3_stream_scope() { ctx->stream = prev; }
+  g3_stream_scope(const g3_stream_scope&) = delete;
+  g3_stream_scope& operator=(const g3_stream_scope&) = delete;
+};
+
+// A sweep with its chain on the context's stream and its bulk updates on `bulk`.  While the object lives the context is
+// marked as inside a sweep: g3i_trsm_rlt then stays on one stream and the event pool cannot be regrown.  The constructor is
+// the opening fork (bulk waits, through `ev`, for everything already queued on the chain's stream: Gram, memsets); check
+// `rc` behind it.  join() is the closing one: the chain continues only after bulk has drained.  An error path needs no
+// join, the caller abandons the sweep.  bulk == the chain's stream is the one-stream mode of a small g3i_potri: no sweep
+// is marked, fork and join do nothing.
+struct g3_sweep_scope {
+  g3_ctx* ctx;
+  hipStream_t chain, bulk;
+  hipEvent_t ev;
+  int rc;
+  g3_sweep_scope(g3_ctx* c, hipStream_t bulk_, hipEvent_t ev_) : ctx(c), chain(c->stream), bulk(bulk_), ev(ev_) {
+    if (bulk != chain) ctx->in_sweep = true;
+    rc = wait(bulk, chain);
+  }
+  ~g3_sweep_scope() {
+    if (bulk != chain) ctx->in_sweep = false;
+  }
+  int join() { return wait(chain, bulk); }
+  g3_sweep_scope(const g3_sweep_scope&) = delete;
+  g3_sweep_scope& operator=(const g3_sweep_scope&) = delete;
+
+ private:
+  int wait(hipStream_t waiter, hipStream_t on) {   // `waiter` goes on only after what is queued on `on` now
+    if (bulk == chain) return G3_OK;
+    G3_HIP(hipEventRecord(ev, on));
+    G3_HIP(hipStreamWaitEvent(waiter, ev, 0));
+    return G3_OK;
+  }
+};
 
 static inline size_t g3_esize(g3_dtype dt) { return dt == G3_F64 ? 8 : 4; }
 static inline int64_t g3_roundup(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
@@ -228,6 +259,8 @@ int g3i_trtri_blocks(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, g3_dtyp
 // except for the last level); all compact (leading dimension n)
 int g3i_trtri_full(g3_ctx* ctx, const void* L, int64_t n, const void* W, void* V, void* Vt, void* U, g3_dtype dt);
 int g3i_reset_info(g3_ctx* ctx);
+// the pivot flag of the factorisation queued last, read on the host (synchronises the context's stream)
+int g3i_read_info(g3_ctx* ctx, int* info_host);
 bool g3i_info_known_zero(const g3_ctx* ctx);
 // g3_diag_stats / g3_logp_terms / g3_rows_dot_ss results left in device memory (no host synchronisation): 3 / 4 doubles
 int g3i_diag_stats_dev(g3_ctx* ctx, const void* A, int64_t n, int64_t ld, g3_dtype dt, double* out_dev);
@@ -242,11 +275,6 @@ size_t g3i_coop_ctl_bytes(int batch);
 int g3i_coop_group(const g3_ctx* ctx, int batch, int64_t np);
 int g3i_coop_factor_batched(g3_ctx* ctx, void* K, int64_t ld, int64_t kstride, void* W, int64_t wstride, unsigned* ctl, int batch,
                             int64_t np, g3_dtype dt);
-#ifdef G3_CHAIN_SERVER
-// true when `info` says the chain server gave up: it is switched off for this context (one line on stderr)
-bool g3i_chain_gave_up(g3_ctx* ctx, int info);
-#define G3_INFO_CHAIN 0x40000000   // pivot-flag value: the chain server gave up (never a pivot index)
-#endif
 int g3i_diag_add(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double value);
 // A[0:rows, 0:cols) *= factor (stream-ordered)
 int g3i_scale(g3_ctx* ctx, void* A, int64_t rows, int64_t cols, int64_t ld, g3_dtype dt, double factor);

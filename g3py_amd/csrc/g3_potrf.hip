@@ -210,16 +210,6 @@ diag128m_kernel(T* A, int64_t ld, int64_t a_stride, T* W, int64_t ldw, int64_t w
 
 constexpr int64_t LB = G3_LB;
 
-static int64_t split_point(int64_t n, int64_t unit) {
-  // n is a multiple of `unit` and > unit; split near the middle on a coarse power-of-two
-  // grid so that large sub-problems keep tile-friendly sizes
-  int64_t g = unit;
-  while (g * 2 <= n / 4 && g < 2048) g *= 2;
-  int64_t n1 = g3_roundup(n / 2, g);
-  if (n1 >= n) n1 = n - unit;
-  return n1;
-}
-
 template <typename T>
 static int potrf_diag(g3_ctx* ctx, T* A, int64_t ld, T* W, int64_t row_base, g3_dtype dt) {
   const int pr = g3i_prof_begin(ctx, G3_TAG_LEAF, 128.0 * 128.0 * 128.0 / 3.0);
@@ -247,7 +237,7 @@ static int trsm_rec(g3_ctx* ctx, const T* L, int64_t n, int64_t ldl, T* B, int64
     // B <- B W^T in place: one tile spans the 128 output columns, so a workgroup has read
     // its rows before it overwrites them
     return g3i_gemm_nt_ex(ctx, B, ldb, B, ldb, W, LB, m, LB, LB, 1.0, 0.0, dt, 0, 1);
-  const int64_t n1 = split_point(n, LB), n2 = n - n1;
+  const int64_t n1 = g3h_split_point(n), n2 = n - n1;
   int rc = trsm_rec<T>(ctx, L, n1, ldl, B, m, ldb, W, dt);
   if (rc) return rc;
   rc = g3i_gemm_nt(ctx, B + n1, ldb, B, ldb, L + n1 * ldl, ldl, m, n2, n1, -1.0, 1.0, dt, 0);
@@ -268,8 +258,8 @@ static int potrf_diag256(g3_ctx* ctx, T* A, int64_t ld, T* W, int64_t row_base) 
 template <typename T>
 static int potrf_rec(g3_ctx* ctx, T* A, int64_t n, int64_t ld, T* W, int64_t row_base, g3_dtype dt) {
   if (n == LB) return potrf_diag<T>(ctx, A, ld, W, row_base, dt);
-  if (n == 2 * LB && ctx->fuse256) return potrf_diag256<T>(ctx, A, ld, W, row_base);
-  const int64_t n1 = split_point(n, LB), n2 = n - n1;
+  if (n == 2 * LB) return potrf_diag256<T>(ctx, A, ld, W, row_base);
+  const int64_t n1 = g3h_split_point(n), n2 = n - n1;
   int rc = potrf_rec<T>(ctx, A, n1, ld, W, row_base, dt);
   if (rc) return rc;
   T* A21 = A + n1 * ld;
@@ -354,29 +344,19 @@ static int potrf_lookahead(g3_ctx* ctx, T* A, int64_t n, int64_t ld, T* W, int64
   std::vector<int> gb;
   g3h_panel_bounds(n, NB, G, ctx->batch, ctx->tune, &bnd, &gb);
   const int nblk = (int)bnd.size() - 1, ngrp = (int)gb.size() - 1;
-  const int nev = 4 * ngrp + 1;
-  if (ctx->la_nev < nev) {
-    if (ctx->la_ev) {
-      for (int i = 0; i < ctx->la_nev; ++i) (void)hipEventDestroy(ctx->la_ev[i]);
-      free(ctx->la_ev);
-    }
-    ctx->la_nev = nev;
-    ctx->la_ev = (hipEvent_t*)calloc(ctx->la_nev, sizeof(hipEvent_t));
-    if (!ctx->la_ev) return G3_ERR_NOMEM;
-    for (int i = 0; i < ctx->la_nev; ++i) G3_HIP(hipEventCreateWithFlags(&ctx->la_ev[i], hipEventDisableTiming));
-  }
+  int rc = g3i_ensure_events(ctx, 4 * ngrp + 1);
+  if (rc) return rc;
   hipEvent_t* evG = ctx->la_ev;                // super-panel s final (stream A)
   hipEvent_t* evB1 = ctx->la_ev + ngrp;        // P1(s) done (stream B)
   hipEvent_t* evB2a = ctx->la_ev + 2 * ngrp;   // P2a(s) done (stream B)
-  hipEvent_t evJoin = ctx->la_ev[4 * ngrp];
-  { const int rs = g3i_ensure_side_stream(ctx); if (rs) return rs; }
+  rc = g3i_ensure_side_stream(ctx);
+  if (rc) return rc;
   hipStream_t sA = ctx->stream, sB = ctx->side_stream;
   auto r = [&](int k) { return k < nblk ? bnd[k] : n; };                 // first column of panel k
   auto c = [&](int s) { return s < ngrp ? bnd[gb[s]] : n; };             // first column of super-panel s
-  int rc = G3_OK;
   // B must not start before everything already queued on A (Gram, memsets) is done
-  G3_HIP(hipEventRecord(evJoin, sA));
-  G3_HIP(hipStreamWaitEvent(sB, evJoin, 0));
+  g3_sweep_scope sweep(ctx, sB, ctx->la_ev[4 * ngrp]);
+  if (sweep.rc) return sweep.rc;
   auto panel = [&](int k) -> int {   // D_k and P_k on stream A
     T* Akk = A + r(k) * ld + r(k);
     const int64_t w = r(k + 1) - r(k);
@@ -417,32 +397,26 @@ static int potrf_lookahead(g3_ctx* ctx, T* A, int64_t n, int64_t ld, T* W, int64
     // ---- stream B: the update with super-panel s of everything to its right
     if (c(s + 1) < n) {
       G3_HIP(hipStreamWaitEvent(sB, evG[s], 0));
-      ctx->stream = sB;
+      g3_stream_scope on_bulk(ctx, sB);
       const int h0 = gb[s + 1];                                       // first panel of super-panel s+1
       rc = update(r(h0 + 1), r(h0 + 1), c(s + 2), c(s), c(s + 1));    // P1(s)
-      if (!rc && hipEventRecord(evB1[s], sB) != hipSuccess) rc = G3_ERR_HIP;
-      if (!rc && c(s + 2) < n) {
+      if (rc) return rc;
+      G3_HIP(hipEventRecord(evB1[s], sB));
+      if (c(s + 2) < n) {
         const int q0 = gb[s + 2];
         rc = update(c(s + 2), c(s + 2), r(q0 + 1), c(s), c(s + 1));   // P2a(s)
-        if (!rc && hipEventRecord(evB2a[s], sB) != hipSuccess) rc = G3_ERR_HIP;
-        if (!rc) rc = update(r(q0 + 1), r(q0 + 1), n, c(s), c(s + 1));   // P2b(s)
-      } else if (!rc && hipEventRecord(evB2a[s], sB) != hipSuccess) {
-        rc = G3_ERR_HIP;
+        if (rc) return rc;
+        G3_HIP(hipEventRecord(evB2a[s], sB));
+        rc = update(r(q0 + 1), r(q0 + 1), n, c(s), c(s + 1));         // P2b(s)
+        if (rc) return rc;
+      } else {
+        G3_HIP(hipEventRecord(evB2a[s], sB));
       }
-      ctx->stream = sA;
-      if (rc) return rc;
     }
   }
   // join: A continues only after B has drained
-  G3_HIP(hipEventRecord(evJoin, sB));
-  G3_HIP(hipStreamWaitEvent(sA, evJoin, 0));
-  return G3_OK;
+  return sweep.join();
 }
-
-#ifdef G3_CHAIN_SERVER   // measurement variant only (scripts/variants/chain_server.inc, scripts/build_variant.sh)
-#include "../../scripts/variants/chain_server.inc"
-#endif
-
 
 int g3i_potrf(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, void* invd) {
   return g3i_potrf_tall(ctx, A, n, ld, dt, invd, 0);
@@ -450,16 +424,11 @@ int g3i_potrf(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, void* in
 
 
 static int64_t g3i_panel_width(g3_ctx* ctx, int64_t n, int* G) {
-  int64_t NB = ctx->nb_lookahead;
   *G = ctx->tune.sb;                 // panels per super-panel
-  if (NB <= 0) {
-    // measured on MI355X (fp64): narrow panels shorten the latency-bound chain of diagonal-block
-    // kernels that dominates small problems, wide panels give the bulk updates more K
-    const bool forced = ctx->tune.nb > 0;
-    NB = forced ? ctx->tune.nb : (n <= 4096 ? 128 : (n <= 6144 ? 256 : (n <= 12288 ? 512 : 1024)));
-    // a batched sweep is bound by work per launch, not by the chain: wider panels again
-    if (!forced && ctx->batch > 1 && NB < 256) NB = 256;
-  }
+  const bool forced = ctx->tune.nb > 0;
+  int64_t NB = forced ? ctx->tune.nb : g3h_default_panel_width(n);
+  // a batched sweep is bound by work per launch, not by the chain: wider panels again
+  if (!forced && ctx->batch > 1 && NB < 256) NB = 256;
   if (*G < 1) *G = 1;
   if (*G > 8) *G = 8;
   return g3_roundup(NB < LB ? LB : NB, LB);
@@ -475,18 +444,11 @@ int g3i_potrf_tall(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, voi
   if (n == 0) return G3_OK;
   // The one-launch 256-wide diagonal kernel shortens the dependency chain (N = 8192: 8.9 -> 8.2 ms when it was
   // introduced); since the round-2 rewrite of the diagonal kernels it is no slower at any size (N = 24576: 95.2 ->
-  // 95.0 ms, 32768: equal), so it is always used.
-  ctx->fuse256 = true;
+  // 95.0 ms, 32768: equal), so potrf_rec always uses it.
 
   int G = 1;
   int64_t NB = g3i_panel_width(ctx, n, &G);
   if (n >= 3 * NB) {
-#ifdef G3_CHAIN_SERVER
-    if (g3i_chain_usable(ctx, n, NB, G)) {
-      if (dt == G3_F64) return potrf_lookahead_chain<double>(ctx, (double*)A, n, ld, (double*)invd, NB, dt, E);
-      return potrf_lookahead_chain<float>(ctx, (float*)A, n, ld, (float*)invd, NB, dt, E);
-    }
-#endif
     if (dt == G3_F64) return potrf_lookahead<double>(ctx, (double*)A, n, ld, (double*)invd, NB, G, dt, E);
     return potrf_lookahead<float>(ctx, (float*)A, n, ld, (float*)invd, NB, G, dt, E);
   }
@@ -509,24 +471,16 @@ template <typename T>
 static int trsm_lookahead(g3_ctx* ctx, const T* L, int64_t n, int64_t ldl, T* B, int64_t m, int64_t ldb, const T* W, g3_dtype dt) {
   const int64_t NBK = 1024;
   const int nblk = (int)((n + NBK - 1) / NBK);
-  if (ctx->la_nev < 2 * nblk + 1) {
-    if (ctx->la_ev) {
-      for (int i = 0; i < ctx->la_nev; ++i) (void)hipEventDestroy(ctx->la_ev[i]);
-      free(ctx->la_ev);
-    }
-    ctx->la_nev = 2 * nblk + 1;
-    ctx->la_ev = (hipEvent_t*)calloc(ctx->la_nev, sizeof(hipEvent_t));
-    if (!ctx->la_ev) return G3_ERR_NOMEM;
-    for (int i = 0; i < ctx->la_nev; ++i) G3_HIP(hipEventCreateWithFlags(&ctx->la_ev[i], hipEventDisableTiming));
-  }
+  int rc = g3i_ensure_events(ctx, 2 * nblk + 1);
+  if (rc) return rc;
   hipEvent_t* evX = ctx->la_ev;            // block j of X solved (stream A)
   hipEvent_t* evU = ctx->la_ev + nblk;     // everything right of block j+1 carries block j (stream B)
-  hipEvent_t evJoin = ctx->la_ev[2 * nblk];
-  { const int rs = g3i_ensure_side_stream(ctx); if (rs) return rs; }
+  rc = g3i_ensure_side_stream(ctx);
+  if (rc) return rc;
   hipStream_t sA = ctx->stream, sB = ctx->side_stream;
   auto c = [&](int j) { return j < nblk ? (int64_t)j * NBK : n; };
-  G3_HIP(hipEventRecord(evJoin, sA));
-  G3_HIP(hipStreamWaitEvent(sB, evJoin, 0));
+  g3_sweep_scope sweep(ctx, sB, ctx->la_ev[2 * nblk]);
+  if (sweep.rc) return sweep.rc;
   auto leaf = [&](int j) -> int {
     return trsm_rec<T>(ctx, L + c(j) * ldl + c(j), c(j + 1) - c(j), ldl, B + c(j), m, ldb, W + (c(j) / LB) * LB * LB, dt);
   };
@@ -535,16 +489,15 @@ static int trsm_lookahead(g3_ctx* ctx, const T* L, int64_t n, int64_t ldl, T* B,
     if (col1 <= col0) return G3_OK;
     return g3i_gemm_nt(ctx, B + col0, ldb, B + c(j), ldb, L + col0 * ldl + c(j), ldl, m, col1 - col0, c(j + 1) - c(j), -1.0, 1.0, dt, 0);
   };
-  int rc = leaf(0);
+  rc = leaf(0);
   if (rc) return rc;
   G3_HIP(hipEventRecord(evX[0], sA));
   for (int j = 0; j + 1 < nblk; ++j) {
     // stream B: block j applied to the blocks right of j+1
     if (c(j + 2) < n) {
       G3_HIP(hipStreamWaitEvent(sB, evX[j], 0));
-      ctx->stream = sB;
+      g3_stream_scope on_bulk(ctx, sB);
       rc = update(j, c(j + 2), n);
-      ctx->stream = sA;
       if (rc) return rc;
     }
     G3_HIP(hipEventRecord(evU[j], sB));
@@ -555,16 +508,16 @@ static int trsm_lookahead(g3_ctx* ctx, const T* L, int64_t n, int64_t ldl, T* B,
     if (rc) return rc;
     G3_HIP(hipEventRecord(evX[j + 1], sA));
   }
-  G3_HIP(hipEventRecord(evJoin, sB));
-  G3_HIP(hipStreamWaitEvent(sA, evJoin, 0));
-  return G3_OK;
+  return sweep.join();
 }
 
 int g3i_trsm_rlt(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, void* B, int64_t m,
                  int64_t ldb, g3_dtype dt, const void* invd) {
   if (n == 0 || m == 0) return G3_OK;
-  // few rows against a long factor, outside batch mode and not from inside a two-stream sweep (side stream free)
-  if (n >= 4096 && m <= 4096 && ctx->batch <= 1 && !g3_on_bulk_stream(ctx)) {
+  // few rows against a long factor, outside batch mode and not from inside a two-stream sweep: that sweep owns the side
+  // stream and the event pool.  Default panels are at most 1024 wide, so a sweep never asks for n >= 4096; with G3_NB >= 4096
+  // a panel solve of g3i_potri does, and takes the one-stream recursion below instead of a sweep nested in its own
+  if (n >= 4096 && m <= 4096 && ctx->batch <= 1 && !ctx->in_sweep) {
     if (dt == G3_F64) return trsm_lookahead<double>(ctx, (const double*)L, n, ldl, (double*)B, m, ldb, (const double*)invd, dt);
     return trsm_lookahead<float>(ctx, (const float*)L, n, ldl, (float*)B, m, ldb, (const float*)invd, dt);
   }
@@ -706,18 +659,10 @@ extern "C" int g3_trsm_full(g3_ctx* ctx, const void* V_dev, int64_t n, int64_t l
   return g3i_gemm_nt_ktri(ctx, X_dev, ldx, B_dev, ldb, V_dev, ldv, m, n, 1.0, 0.0, dt);
 }
 
-static int read_info(g3_ctx* ctx, int* info_host) {
+int g3i_read_info(g3_ctx* ctx, int* info_host) {
   G3_HIP(hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   G3_HIP(hipStreamSynchronize(ctx->stream));
   *info_host = *ctx->h_info;
-#ifdef G3_CHAIN_SERVER
-  if (g3i_chain_gave_up(ctx, *info_host)) {
-    // the matrix was being factored in place: the caller must supply it again (the server is off from now on)
-    (void)g3i_reset_info(ctx);
-    snprintf(ctx->err, sizeof(ctx->err), "the resident chain workgroups gave up; the factorisation is incomplete -- call again");
-    return G3_ERR_HIP;
-  }
-#endif
   return G3_OK;
 }
 
@@ -736,7 +681,7 @@ extern "C" int g3_potrf(g3_ctx* ctx, void* A_dev, int64_t n, int64_t ld, g3_dtyp
   }
   int rc = g3i_potrf(ctx, A_dev, n, ld, dt, invd_dev);
   if (rc) return rc;
-  return read_info(ctx, info_host);
+  return g3i_read_info(ctx, info_host);
 }
 
 // the first non-zero info of a sequence of factorisations, kept on the device
@@ -762,19 +707,11 @@ extern "C" int g3_potrf_nowait(g3_ctx* ctx, void* A_dev, int64_t n, int64_t ld, 
     // 256-wide kernel) instead of the two-stream sweep tuned for a stand-alone small matrix
     G3_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int) * g3_nbatch(ctx), ctx->stream));
     ctx->info_clean = false;
-    ctx->fuse256 = true;
     if (n == 0) rc = G3_OK;
     else if (dt == G3_F64) rc = potrf_rec<double>(ctx, (double*)A_dev, n, ld, (double*)invd_dev, 0, dt);
     else rc = potrf_rec<float>(ctx, (float*)A_dev, n, ld, (float*)invd_dev, 0, dt);
   } else {
-#ifdef G3_CHAIN_SERVER
-    const bool broken = ctx->chain_broken;
-    ctx->chain_broken = true;              // (the flag of this call is read much later: no resident workgroups here)
-#endif
     rc = g3i_potrf(ctx, A_dev, n, ld, dt, invd_dev);
-#ifdef G3_CHAIN_SERVER
-    ctx->chain_broken = broken;
-#endif
   }
   if (rc) return rc;
   hipLaunchKernelGGL(info_merge_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_info, info_accum_dev);
@@ -864,19 +801,7 @@ static int robust_t(g3_ctx* ctx, const T* K, int64_t ldk, T* L, int64_t ldl, int
     G3_LAUNCH_CHECK();
     int r = g3i_potrf(ctx, F, np, ldf, dt, ctx->invd);
     if (r) return r;
-#ifdef G3_CHAIN_SERVER
-    const bool chain_was_on = !ctx->chain_broken;
-#endif
-    r = read_info(ctx, info);
-#ifdef G3_CHAIN_SERVER
-    if (r == G3_ERR_HIP && chain_was_on && ctx->chain_broken) {        // once: the copy above is simply made again
-      hipLaunchKernelGGL((copy_lower_pad_kernel<T>), grid, dim3(256), 0, ctx->stream, F, ldf, K, ldk, n, np, (T)add);
-      G3_LAUNCH_CHECK();
-      r = g3i_potrf(ctx, F, np, ldf, dt, ctx->invd);
-      if (!r) r = read_info(ctx, info);
-    }
-#endif
-    return r;
+    return g3i_read_info(ctx, info);
   };
   int info = 0, tries = 0, fallback = 0;
   double jitter = 0.0;
@@ -952,7 +877,3 @@ extern "C" int g3_potrf_robust(g3_ctx* ctx, const void* K_dev, int64_t ldk, void
   return robust_t<float>(ctx, (const float*)K_dev, ldk, (float*)L_dev, ldl, n, dt, maxtries,
                          tries_host, fallback_host, jitter_host);
 }
-
-#ifdef G3_PROBE   // measurement build only: the round-4 feasibility probes (scripts/variants/probe_resident.inc)
-#include "../../scripts/variants/probe_resident.inc"
-#endif

@@ -2,7 +2,7 @@
 // shim"): g3py_amd/csrc/g3_host.h is pure C++ and is compiled here with g++ -fsanitize=address,undefined.  Every
 // table / schedule builder is driven over the shapes the library produces (and some it never should) and its output
 // is checked the way the device consumes it: the tile lookup of the GEMM kernel, the op list of the stripe solve, the
-// chunking of the multi-GPU staircase, panel boundaries, the fast-path matcher, the program ring, the jitter schedule, the layout
+// chunking of the multi-GPU staircase, the recursion's split point, the panel-width ladder, panel boundaries, the fast-path matcher, the program ring, the jitter schedule, the layout
 // of the batched entry points' device buffer and the host expansion of a chain member.
 // TEST INFRASTRUCTURE: never linked into the product.
 #include <math.h>
@@ -249,6 +249,19 @@ static void test_trsm_ops() {
   }
 }
 
+// the two schedule rules the sweeps share: the recursion's split point and the default panel-width ladder
+static void test_split_and_ladder() {
+  for (int64_t n = 256; n <= 4096; n += 128) {
+    const int64_t n1 = g3h_split_point(n);
+    CHECK(n1 >= 128 && n1 <= n - 128);
+    CHECK(n1 % 128 == 0);
+  }
+  const int64_t split[][2] = {{256, 128}, {384, 256}, {640, 384}, {1024, 512}, {2048, 1024}, {3072, 1536}};
+  for (auto& p : split) CHECK(g3h_split_point(p[0]) == p[1]);
+  const int64_t ladder[][2] = {{4096, 128}, {4224, 256}, {6144, 256}, {6272, 512}, {12288, 512}, {12416, 1024}};
+  for (auto& p : ladder) CHECK(g3h_default_panel_width(p[0]) == p[1]);
+}
+
 static void test_panel_bounds() {
   for (int64_t n = 128; n <= 70000; n += (n < 2048 ? 128 : 11 * 128 + (n % 1024)))
     for (int64_t NB : {128, 256, 512, 1024, 2048})
@@ -450,6 +463,7 @@ int main(int argc, char** argv) {
   test_dealing();
   test_rasters();
   test_trsm_ops();
+  test_split_and_ladder();
   test_panel_bounds();
   test_match_and_validate();
   test_ring_and_jitter();

@@ -221,7 +221,9 @@ def test_potrf_info_is_the_first_failing_pivot(dev, n):
     assert dev.potrf(dev.upload(K), n) == 10
 
 
-@pytest.mark.parametrize('n,m', [(128, 128), (384, 256), (1024, 128), (2048, 384)])
+# (4096, 128) and (4224, 256): the smallest shapes that take the two-stream solve over 1024-column blocks (four full blocks;
+# five with a 128-wide last one)
+@pytest.mark.parametrize('n,m', [(128, 128), (384, 256), (1024, 128), (2048, 384), (4096, 128), (4224, 256)])
 def test_trsm_rlt(dev, n, m):
     rng = np.random.default_rng(n + m)
     L = scipy.linalg.cholesky(_spd(rng, n), lower=True)
