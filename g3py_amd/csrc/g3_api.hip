@@ -190,11 +190,9 @@ extern "C" int g3_ctx_destroy(g3_ctx* ctx) {
 // has synchronised it; forget every reference -- the program ring records its events on the stream a slot was consumed on
 void g3i_ctx_forget_stream(g3_ctx* ctx, hipStream_t s) {
   if (!ctx || !s) return;
-  if (ctx->prog_stream == s) {
-    for (int i = 0; i < G3_PROG_SLOTS; ++i) ctx->prog_busy[i] = false;
-    ctx->prog_last = -1;
-    ctx->prog_stream = nullptr;
-  }
+  g3h_ring_forget(ctx->prog_busy, G3_PROG_SLOTS, &ctx->prog_last, ctx->prog_stream == s,
+                  [&](int i) { return hipEventQuery(ctx->prog_ev[i]) == hipSuccess; });
+  if (ctx->prog_stream == s) ctx->prog_stream = nullptr;
   if (ctx->info_stream == s) {
     ctx->info_clean = false;
     ctx->info_stream = nullptr;

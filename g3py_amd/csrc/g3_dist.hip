@@ -20,360 +20,11 @@
 //   look-ahead    c.  (after B_k) the owner of block k+2 applies panel k+1 to its diagonal block from its own
 //   stream            rows, factors it and broadcasts factor + 128 x 128 block inverses
 //
-// Transports: RCCL (the product) or caller-supplied host callbacks (tests: several ranks sharing ONE GPU over
-// gloo -- RCCL refuses two ranks on one device -- so the schedule is checked for P > 1 on a one-GPU box).
-#include "g3_internal.h"
-#include "g3_host.h"
+// Transports (g3_dist_transport.h): RCCL (the product) or caller-supplied host callbacks (tests: several ranks sharing ONE
+// GPU over gloo); the replay transport, which plays one rank out of a world-1 driver's factor, is below.
+#include "g3_dist_transport.h"
 
-#include <dlfcn.h>
 #include <math.h>
-#include <rccl/rccl.h>
-#include <stdlib.h>
-#include <time.h>
-
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-namespace {
-
-// ---------------------------------------------------------------------------------------- transports
-enum { G3_COLL_BCAST = 0, G3_COLL_ALLGATHER = 1, G3_COLL_ALLREDUCE = 2, G3_NCOLL = 3, G3_PH_DIAG = 3, G3_PH_SOLVE = 4, G3_NKIND = 5 };
-
-struct Transport {
-  virtual ~Transport() {}
-  // stream-ordered after everything queued on s; the result is visible to work queued on s afterwards
-  virtual int bcast(void* buf, size_t bytes, int root, hipStream_t s) = 0;
-  virtual int allgather(const void* send, void* recv, size_t bytes_per_rank, hipStream_t s) = 0;
-  // host values in / out; synchronises s.  op: 0 sum, 1 min, 2 max
-  virtual int allreduce(double* host, int n, int op, hipStream_t s) = 0;
-  virtual const char* name() const = 0;
-  // what the NEXT collective carries (G3_HINT_*, index of the block / panel): only the replay transport needs to know
-  virtual void hint(int what, int index) { (void)what; (void)index; }
-  char err[256] = {0};
-};
-enum { G3_HINT_NONE = 0, G3_HINT_DIAG = 1, G3_HINT_PANEL = 2, G3_HINT_AVEC = 3 };
-
-struct RcclApi {
-  void* h = nullptr;
-  decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-  decltype(&ncclCommInitRank) CommInitRank = nullptr;
-  decltype(&ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&ncclCommAbort) CommAbort = nullptr;      // optional
-  decltype(&ncclBroadcast) Broadcast = nullptr;
-  decltype(&ncclAllGather) AllGather = nullptr;
-  decltype(&ncclAllReduce) AllReduce = nullptr;
-  decltype(&ncclGetErrorString) GetErrorString = nullptr;
-};
-
-static RcclApi* rccl_api(char* err, size_t errlen) {
-  static RcclApi api;
-  static int state = 0;   // 0 untried, 1 ok, -1 failed
-  if (state == 1) return &api;
-  if (state == -1) return nullptr;
-  // a copy already loaded into the process (e.g. the one PyTorch ships) is reused; G3_RCCL_PATH overrides
-  const char* forced = getenv("G3_RCCL_PATH");
-  const bool only = forced && *forced;          // a path given explicitly is the ONLY candidate: a wrong one fails loudly
-  const char* names[] = {forced, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-  for (int pass = 0; pass < 2 && !api.h; ++pass)
-    for (const char* n : names) {
-      if (!n || !*n) continue;
-      if (only && n != forced) break;
-      api.h = dlopen(n, RTLD_NOW | RTLD_GLOBAL | (pass == 0 ? RTLD_NOLOAD : 0));
-      if (api.h) break;
-    }
-  if (!api.h) {
-    snprintf(err, errlen, "librccl not found (set G3_RCCL_PATH): %s", dlerror());
-    state = -1;
-    return nullptr;
-  }
-#define G3_SYM(f)                                                        \
-  api.f = (decltype(api.f))dlsym(api.h, "nccl" #f);                      \
-  if (!api.f) {                                                          \
-    snprintf(err, errlen, "librccl lacks nccl" #f);                      \
-    state = -1;                                                          \
-    return nullptr;                                                      \
-  }
-  G3_SYM(GetUniqueId) G3_SYM(CommInitRank) G3_SYM(CommDestroy) G3_SYM(Broadcast) G3_SYM(AllGather) G3_SYM(AllReduce)
-  G3_SYM(GetErrorString)
-#undef G3_SYM
-  api.CommAbort = (decltype(api.CommAbort))dlsym(api.h, "ncclCommAbort");
-  state = 1;
-  return &api;
-}
-
-struct RcclTransport : Transport {
-  RcclApi* api = nullptr;
-  ncclComm_t comm_gather = nullptr;   // panel all-gathers, scalar all-reduces (chain stream)
-  ncclComm_t comm_bcast = nullptr;    // diagonal-factor broadcasts (look-ahead stream): never queues behind a gather
-  double* scratch = nullptr;          // device scratch of the scalar all-reduces
-  double* hscratch = nullptr;         // pinned
-  static const int SCR = 16384;
-  bool failed = false;                // an evaluation returned an error on this rank: peers may be inside a collective
-  ~RcclTransport() override {
-    // after a local error the communicators are ABORTED, not destroyed: ncclCommDestroy waits for outstanding
-    // collectives, which the peers of a rank that left the sweep will never complete.  (A failed rank must end the job:
-    // the other ranks are by then blocked on the GPU in a collective this rank did not enter.)
-    auto drop = [&](ncclComm_t c) { if (failed && api->CommAbort) api->CommAbort(c); else api->CommDestroy(c); };
-    if (api && comm_gather) drop(comm_gather);
-    if (api && comm_bcast) drop(comm_bcast);
-    if (scratch) (void)hipFree(scratch);
-    if (hscratch) (void)hipHostFree(hscratch);
-  }
-  int chk(ncclResult_t r, const char* what) {
-    if (r == ncclSuccess) return G3_OK;
-    snprintf(err, sizeof(err), "%s: %s", what, api->GetErrorString(r));
-    return G3_ERR_HIP;
-  }
-  int bcast(void* buf, size_t bytes, int root, hipStream_t s) override {
-    return chk(api->Broadcast(buf, buf, bytes, ncclChar, root, comm_bcast, s), "ncclBroadcast");
-  }
-  int allgather(const void* send, void* recv, size_t bytes, hipStream_t s) override {
-    return chk(api->AllGather(send, recv, bytes, ncclChar, comm_gather, s), "ncclAllGather");
-  }
-  int allreduce(double* host, int n, int op, hipStream_t s) override {
-    for (int off = 0; off < n; off += SCR) {
-      const int c = n - off < SCR ? n - off : SCR;
-      memcpy(hscratch, host + off, c * sizeof(double));
-      if (hipMemcpyAsync(scratch, hscratch, c * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) return G3_ERR_HIP;
-      const ncclRedOp_t o = op == 0 ? ncclSum : (op == 1 ? ncclMin : ncclMax);
-      int rc = chk(api->AllReduce(scratch, scratch, c, ncclDouble, o, comm_gather, s), "ncclAllReduce");
-      if (rc) return rc;
-      if (hipMemcpyAsync(hscratch, scratch, c * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) return G3_ERR_HIP;
-      if (hipStreamSynchronize(s) != hipSuccess) return G3_ERR_HIP;
-      memcpy(host + off, hscratch, c * sizeof(double));
-    }
-    return G3_OK;
-  }
-  const char* name() const override { return "rccl"; }
-};
-
-struct CallbackTransport : Transport {
-  g3_dist_callbacks cb;
-  int bcast(void* buf, size_t bytes, int root, hipStream_t s) override {
-    if (hipStreamSynchronize(s) != hipSuccess) return G3_ERR_HIP;
-    return cb.bcast(cb.user, buf, bytes, root) ? G3_ERR_HIP : G3_OK;
-  }
-  int allgather(const void* send, void* recv, size_t bytes, hipStream_t s) override {
-    if (hipStreamSynchronize(s) != hipSuccess) return G3_ERR_HIP;
-    return cb.allgather(cb.user, send, recv, bytes) ? G3_ERR_HIP : G3_OK;
-  }
-  int allreduce(double* host, int n, int op, hipStream_t s) override {
-    if (hipStreamSynchronize(s) != hipSuccess) return G3_ERR_HIP;
-    return cb.allreduce(cb.user, host, n, op) ? G3_ERR_HIP : G3_OK;
-  }
-  const char* name() const override { return "callbacks"; }
-};
-
-// ---- asynchronous host-callback transport: the collectives as jobs of two worker threads (gather / all-reduce, and
-// broadcast: the product's two communicators), stream-ordered like RCCL calls.
-//   issue (host thread):  record E on the stream -> queue the job -> launch a one-wave kernel on the stream that waits for
-//                         the worker's ticket (a word in pinned host memory) -> return: the host runs ahead
-//   worker:               wait for E -> device -> pinned staging (its own copy stream) -> callback -> staging -> device
-//                         -> publish the ticket: the stream goes on
-// The wait kernel has a wall-clock limit (G3_DIST_ASYNC_TIMEOUT_S, default 120 s): a stream never hangs on a dead peer, the
-// limit sets a device error word that every later transport call reports.  The workers' copy streams have NORMAL priority:
-// HIP keeps separate hardware-queue pools per priority, so they never sit behind a waiting high- or low-priority stream of
-// the driver.
-__global__ void host_ticket_wait_kernel(const unsigned* ticket, unsigned want, unsigned long long limit, unsigned* err) {
-  if (threadIdx.x != 0) return;
-  const unsigned long long t0 = wall_clock64();
-  unsigned spins = 0;
-  while (__hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < want) {
-    __builtin_amdgcn_s_sleep(8);
-    if ((++spins & 63u) == 0 && wall_clock64() - t0 > limit) {
-      __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      break;
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-}
-
-struct AsyncCallbackTransport : Transport {
-  g3_dist_host_callbacks cb;
-  int device = 0, rank = 0, world = 1;
-  struct Job {
-    int kind = -1;                 // G3_COLL_*; -1: quit
-    hipEvent_t ev = nullptr;
-    void* buf = nullptr;           // bcast buffer / all-gather receive buffer (device)
-    const void* send = nullptr;    // all-gather: this rank's part (device)
-    size_t bytes = 0;
-    int root = 0;
-    double* vals = nullptr;        // all-reduce (host, the caller waits)
-    int n = 0, op = 0;
-    unsigned seq = 0;
-  };
-  struct Worker {
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv, cv_done;
-    std::deque<Job> q;
-    unsigned issued = 0, done = 0;       // tickets (done is mirrored in *ticket for the device)
-    unsigned* ticket = nullptr;          // pinned, mapped
-    unsigned* ticket_dev = nullptr;
-    hipStream_t cs = nullptr;            // copy stream
-    char* stage = nullptr;               // pinned staging
-    size_t stage_bytes = 0;
-    std::vector<char*> retired;          // outgrown staging buffers: released at teardown (hipHostFree synchronises the
-                                         // DEVICE -- called while a stream waits for this worker it would never return)
-    int failed = 0;
-    char msg[200] = {0};
-  } w[2];                                // 0: all-gather + all-reduce, 1: broadcast
-  unsigned* err_host = nullptr;          // pinned: a wait kernel ran into its limit
-  unsigned* err_dev = nullptr;
-  unsigned long long limit = 12000000000ull;
-  std::vector<hipEvent_t> evpool;
-  std::mutex evmu;
-
-  int start() {
-    if (hipHostMalloc((void**)&err_host, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return G3_ERR_HIP;
-    *err_host = 0;
-    if (hipHostGetDevicePointer((void**)&err_dev, err_host, 0) != hipSuccess) return G3_ERR_HIP;
-    const int lim = g3h_env_int("G3_DIST_ASYNC_TIMEOUT_S", 120);
-    limit = (unsigned long long)(lim > 0 ? lim : 120) * 100000000ull;      // wall_clock64 ticks at 100 MHz
-    for (int i = 0; i < 2; ++i) {
-      if (hipHostMalloc((void**)&w[i].ticket, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return G3_ERR_HIP;
-      *w[i].ticket = 0;
-      if (hipHostGetDevicePointer((void**)&w[i].ticket_dev, w[i].ticket, 0) != hipSuccess) return G3_ERR_HIP;
-      if (hipStreamCreateWithFlags(&w[i].cs, hipStreamNonBlocking) != hipSuccess) return G3_ERR_HIP;
-      w[i].th = std::thread([this, i]() { run(i); });
-    }
-    return G3_OK;
-  }
-  ~AsyncCallbackTransport() override {
-    for (int i = 0; i < 2; ++i) {
-      if (w[i].th.joinable()) {
-        { std::lock_guard<std::mutex> lk(w[i].mu); w[i].q.push_back(Job()); }
-        w[i].cv.notify_all();
-        w[i].th.join();
-      }
-      if (w[i].cs) { (void)hipStreamSynchronize(w[i].cs); (void)hipStreamDestroy(w[i].cs); }
-      if (w[i].stage) (void)hipHostFree(w[i].stage);
-      for (char* p : w[i].retired) (void)hipHostFree(p);
-      if (w[i].ticket) (void)hipHostFree(w[i].ticket);
-    }
-    for (hipEvent_t e : evpool) (void)hipEventDestroy(e);
-    if (err_host) (void)hipHostFree(err_host);
-  }
-  hipEvent_t take_event() {
-    std::lock_guard<std::mutex> lk(evmu);
-    if (!evpool.empty()) { hipEvent_t e = evpool.back(); evpool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-    return e;
-  }
-  void give_event(hipEvent_t e) { std::lock_guard<std::mutex> lk(evmu); evpool.push_back(e); }
-  bool ensure_stage(Worker& W, size_t bytes) {
-    if (W.stage_bytes >= bytes) return true;
-    if (W.stage) W.retired.push_back(W.stage);       // (not freed here: see `retired`)
-    W.stage = nullptr; W.stage_bytes = 0;
-    bytes += bytes / 4;                              // head room: plans of one driver differ by a few blocks
-    if (hipHostMalloc((void**)&W.stage, bytes, hipHostMallocDefault) != hipSuccess) return false;
-    W.stage_bytes = bytes;
-    return true;
-  }
-  void fail(Worker& W, const char* what) {
-    W.failed = 1;
-    snprintf(W.msg, sizeof(W.msg), "%s", what);
-  }
-  void run(int i) {
-    Worker& W = w[i];
-    (void)hipSetDevice(device);
-    for (;;) {
-      Job j;
-      {
-        std::unique_lock<std::mutex> lk(W.mu);
-        W.cv.wait(lk, [&]() { return !W.q.empty(); });
-        j = W.q.front();
-        W.q.pop_front();
-      }
-      if (j.kind < 0) return;
-      bool ok = !W.failed;
-      if (j.ev) {
-        if (hipEventSynchronize(j.ev) != hipSuccess) { ok = false; fail(W, "waiting for the stream failed"); }
-        give_event(j.ev);
-      }
-      if (ok && j.kind == G3_COLL_BCAST) {
-        ok = ensure_stage(W, j.bytes);
-        if (ok && rank == j.root) ok = hipMemcpyAsync(W.stage, j.buf, j.bytes, hipMemcpyDeviceToHost, W.cs) == hipSuccess && hipStreamSynchronize(W.cs) == hipSuccess;
-        if (ok) ok = cb.bcast(cb.user, W.stage, j.bytes, j.root) == 0;
-        if (ok && rank != j.root) ok = hipMemcpyAsync(j.buf, W.stage, j.bytes, hipMemcpyHostToDevice, W.cs) == hipSuccess && hipStreamSynchronize(W.cs) == hipSuccess;
-        if (!ok && !W.failed) fail(W, "broadcast failed (staging copy or callback)");
-      } else if (ok && j.kind == G3_COLL_ALLGATHER) {
-        ok = ensure_stage(W, j.bytes * (size_t)world);
-        char* mine = W.stage + (size_t)rank * j.bytes;
-        if (ok) ok = hipMemcpyAsync(mine, j.send, j.bytes, hipMemcpyDeviceToHost, W.cs) == hipSuccess && hipStreamSynchronize(W.cs) == hipSuccess;
-        if (ok) ok = cb.allgather(cb.user, mine, W.stage, j.bytes) == 0;
-        // everything but this rank's own part goes back (the in-place gather leaves that where it is; an out-of-place
-        // one -- send outside the receive buffer -- gets the local copy as well)
-        const bool inplace = (const char*)j.send == (const char*)j.buf + (size_t)rank * j.bytes;
-        for (int q = 0; q < world && ok; ++q)
-          if (q != rank || !inplace)
-            ok = hipMemcpyAsync((char*)j.buf + (size_t)q * j.bytes, W.stage + (size_t)q * j.bytes, j.bytes, hipMemcpyHostToDevice, W.cs) == hipSuccess;
-        if (ok) ok = hipStreamSynchronize(W.cs) == hipSuccess;
-        if (!ok && !W.failed) fail(W, "all-gather failed (staging copy or callback)");
-      } else if (ok && j.kind == G3_COLL_ALLREDUCE) {
-        ok = cb.allreduce(cb.user, j.vals, j.n, j.op) == 0;
-        if (!ok && !W.failed) fail(W, "all-reduce callback failed");
-      }
-      // the ticket is published even after a failure: a stream must never be left waiting (the failure is reported by
-      // the next transport call and ends the evaluation with an error)
-      {
-        std::lock_guard<std::mutex> lk(W.mu);
-        W.done = j.seq;
-        __atomic_store_n(W.ticket, j.seq, __ATOMIC_RELEASE);
-      }
-      W.cv_done.notify_all();
-    }
-  }
-  int check() {
-    for (int i = 0; i < 2; ++i)
-      if (w[i].failed) { snprintf(err, sizeof(err), "%s", w[i].msg); return G3_ERR_HIP; }
-    if (*err_host) { snprintf(err, sizeof(err), "a stream waited longer than the limit for a collective (peer gone?)"); return G3_ERR_HIP; }
-    return G3_OK;
-  }
-  int issue(int wi, Job j, hipStream_t s) {
-    int rc = check();
-    if (rc) return rc;
-    Worker& W = w[wi];
-    j.ev = take_event();
-    if (!j.ev || hipEventRecord(j.ev, s) != hipSuccess) { snprintf(err, sizeof(err), "event record failed"); return G3_ERR_HIP; }
-    {
-      std::lock_guard<std::mutex> lk(W.mu);
-      j.seq = ++W.issued;
-      W.q.push_back(j);
-    }
-    W.cv.notify_all();
-    hipLaunchKernelGGL(host_ticket_wait_kernel, dim3(1), dim3(64), 0, s, (const unsigned*)W.ticket_dev, j.seq, limit, err_dev);
-    if (hipGetLastError() != hipSuccess) { snprintf(err, sizeof(err), "wait-kernel launch failed"); return G3_ERR_HIP; }
-    return G3_OK;
-  }
-  int bcast(void* buf, size_t bytes, int root, hipStream_t s) override {
-    Job j; j.kind = G3_COLL_BCAST; j.buf = buf; j.bytes = bytes; j.root = root;
-    return issue(1, j, s);
-  }
-  int allgather(const void* send, void* recv, size_t bytes, hipStream_t s) override {
-    Job j; j.kind = G3_COLL_ALLGATHER; j.send = send; j.buf = recv; j.bytes = bytes;
-    return issue(0, j, s);
-  }
-  int allreduce(double* host, int n, int op, hipStream_t s) override {
-    // behind everything queued on s and behind every gather issued so far; the caller needs the values: wait here
-    Job j; j.kind = G3_COLL_ALLREDUCE; j.vals = host; j.n = n; j.op = op;
-    int rc = issue(0, j, s);
-    if (rc) return rc;
-    Worker& W = w[0];
-    unsigned want;
-    { std::lock_guard<std::mutex> lk(W.mu); want = W.issued; }
-    { std::unique_lock<std::mutex> lk(W.mu); W.cv_done.wait(lk, [&]() { return W.done >= want; }); }
-    if (hipStreamSynchronize(s) != hipSuccess) return G3_ERR_HIP;
-    return check();
-  }
-  const char* name() const override { return "callbacks-async"; }
-};
-
-}  // namespace
 
 // ---------------------------------------------------------------------------------------- the driver object
 struct g3_dist {
@@ -391,10 +42,9 @@ struct g3_dist {
   // queue -- and which of the chip's compute pipes -- a stream lands on is decided by creation order, and the same replayed
   // rank measured 36.9 or 42.1 ms (config 4, P = 8, one box) depending on how many streams the process had created before
   // the driver's.  Three consecutive creations keep the three streams of the sweep on distinct queues whatever the caller
-  // did; its stream only brackets an entry point (ChainScope).  G3_DIST_OWN_CHAIN=0: the chain on the caller's stream.
+  // did; its stream only brackets an entry point (ChainScope).
   hipStream_t s_chain = nullptr;
   hipEvent_t ev_bracket = nullptr;
-  std::vector<hipStream_t> pad_streams;   // G3_DIST_PAD_STREAMS=n (measurements): n idle streams created in front of the three
   int rank = 0, world = 1;
   Transport* tr = nullptr;
   // plan
@@ -409,7 +59,6 @@ struct g3_dist {
   int64_t rows_mat = 0, rows_rhs = 0, cmax = 1;
   char* A = nullptr;            // (rows_mat + rows_rhs) x Np local rows, full width
   char* dbuf[2] = {nullptr, nullptr};   // nb x nb diagonal factor + nb x 128 block inverses
-  char* send[2] = {nullptr, nullptr};
   char* gath[3] = {nullptr, nullptr, nullptr};
   char* avec = nullptr;         // 1 x Np: a = L^-1 delta, broadcast for the mean
   char* dots = nullptr;         // 2 x 128 scratch of rows_dot_ss, one pair per right-hand-side chunk of this rank
@@ -431,7 +80,6 @@ struct g3_dist {
   char* vt = nullptr;           // nb x nb scratch of the inversion: V^T
   char* ubuf = nullptr;         // nb x nb scratch of the inversion: (L21 V11)^T per pair
   char* rbuf = nullptr;         // (rows_rhs + rows_inv) x nb: the right-hand-side rows of a panel, solved out of place
-  int deal_snake = 0;           // G3_DIST_DEAL=snake (read at creation): the round-4 dealing, for A/B measurements
   int plan_gen = 0;             // bumped by every g3_dist_plan: a replay notices a re-planned reference
   int replay_refs = 0;          // replay drivers that read this driver's factor: it refuses re-plan / destroy meanwhile
   // phases timed with the collectives' event machinery: 3 = a diagonal block's update + factorisation, 4 = a panel solve
@@ -442,6 +90,7 @@ struct g3_dist {
   char* Kinv = nullptr;         // rows_mat x Np
   char* alpha_dev = nullptr;    // 1 x Np: alpha = K^-1 delta (scaled), global order
   char* agath = nullptr;        // world x cmax_all x nb: gathered alpha pieces
+  char* asend = nullptr;        // cmax_all x nb: this rank's alpha pieces, as it sends them
   std::vector<hipEvent_t> ev;   // B_k events + stream joins
   // accounting: per collective kind calls, bytes (sent + received by this rank), device milliseconds
   double n_calls[G3_NKIND] = {0, 0, 0, 0, 0}, n_bytes[G3_NKIND] = {0, 0, 0, 0, 0};
@@ -503,13 +152,11 @@ struct ChainScope {
   g3_dist* D;
   hipStream_t user;
   explicit ChainScope(g3_dist* D_) : D(D_), user(D_->ctx->stream) {
-    if (!D->s_chain) return;
     (void)hipEventRecord(D->ev_bracket, user);
     (void)hipStreamWaitEvent(D->s_chain, D->ev_bracket, 0);
     D->ctx->stream = D->s_chain;
   }
   ~ChainScope() {
-    if (!D->s_chain) return;
     (void)hipEventRecord(D->ev_bracket, D->s_chain);
     (void)hipStreamWaitEvent(user, D->ev_bracket, 0);
     D->ctx->stream = user;
@@ -539,6 +186,30 @@ static inline size_t dbuf_bytes(const g3_dist* D) { return ((size_t)D->nb * D->n
 // what travels: V alone with the full inverse (the owner keeps L in its matrix), else L and the block inverses
 static inline char* bc_ptr(const g3_dist* D, int k) { return D->fullinv ? Vof(D, k) : D->dbuf[k % 2]; }
 static inline size_t bc_bytes(const g3_dist* D) { return (D->fullinv ? (size_t)D->nb * D->nb : (size_t)D->nb * D->nb + (size_t)D->nb * 128) * D->es; }
+
+// rows of block I that belong to the N x N matrix (the rest of its nb rows is identity padding)
+static inline int64_t valid_rows(const g3_dist* D, int I) {
+  const int64_t nv = D->N - (int64_t)I * D->nb;
+  return nv < 0 ? 0 : (nv < D->nb ? nv : D->nb);
+}
+// block I of the (zeroed) row region that starts at local row `base`: v on the valid part of its diagonal, 1 on the padding.
+// identity: the caller's v IS that 1, so one launch writes both parts
+static int set_block_diag(g3_dist* D, int64_t base, int I, double v, bool identity = false) {
+  const int64_t nv = identity ? D->nb : valid_rows(D, I);
+  char* Dg = Aat(D, base + D->loff[I], (int64_t)I * D->nb);
+  if (nv > 0) G3D_RC(D->ctx, g3_diag_add(D->ctx, Dg, nv, D->Np, D->dt, v));
+  if (nv < D->nb) G3D_RC(D->ctx, g3_diag_add(D->ctx, Dg + ((size_t)nv * D->Np + nv) * D->es, D->nb - nv, D->Np, D->dt, 1.0));
+  return G3_OK;
+}
+// element i of a host buffer of the plan's type
+static inline double host_at(const g3_dist* D, const void* h, size_t i) {
+  return D->dt == G3_F64 ? ((const double*)h)[i] : (double)((const float*)h)[i];
+}
+// f(T()) with T the plan's type: the launches of this file's own kernel templates
+template <typename F>
+static inline void by_dtype(const g3_dist* D, F f) {
+  if (D->dt == G3_F64) f(double()); else f(float());
+}
 
 // all blocks of a panel that other ranks would send, in ONE launch (a hipMemcpy2DAsync per 2 MB block costs ~20 us each:
 // 70 ms per evaluation at nb = 512, which would be the replay's own artefact, not the schedule's)
@@ -689,10 +360,18 @@ static int do_allreduce(g3_dist* D, double* host, int n, int op) {
 // shows as the small kernel's latency jumping from ~20 us to a large part of the long kernel's duration.  The three streams
 // of the sweep are a triple with no sharing; the rest are destroyed.  ~60 ms once per driver; G3_DIST_PROBE=0 takes the
 // first of each (G3_DIST_PROBE_LOG=1 prints the matrix).
-// picks (chain, look, bulk) out of freshly created candidates; on any failure falls back to the first of each
-static int pick_streams(g3_dist* D, int lo, int hi, bool own_chain) {
+// picks (chain, look, bulk, masked bulk) out of freshly created candidates and destroys the rest.  A candidate or the probe's
+// scratch that cannot be created, or device properties that cannot be read, is G3_ERR_HIP with nothing left behind; a probe
+// measurement that fails (or G3_DIST_PROBE=0) takes the first of each
+static int pick_streams(g3_dist* D, int lo, int hi) {
   const int NH = 4, NL = 8, NLP = 4;      // low candidates 0 .. NLP-1: plain low priority; NLP .. NL-1: CU-masked (if any)
   hipStream_t H[NH] = {nullptr, nullptr, nullptr, nullptr}, L[NL] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  unsigned* scratch = nullptr;
+  auto cleanup = [&](int kc, int kl, int kb, int kb2) {
+    for (int i = 0; i < NH; ++i) if (H[i] && i != kc && i != kl) (void)hipStreamDestroy(H[i]);
+    for (int i = 0; i < NL; ++i) if (L[i] && i != kb && i != kb2) (void)hipStreamDestroy(L[i]);
+    if (scratch) (void)hipFree(scratch);
+  };
   hipError_t e = hipSuccess;
   for (int i = 0; i < NH && e == hipSuccess; ++i) e = hipStreamCreateWithPriority(&H[i], hipStreamNonBlocking, hi);
   // From six ranks on a bulk stream exists that may not use 32 of the 256 CUs (mask bit i = CU i div 8 of XCC i mod 8: the
@@ -704,76 +383,70 @@ static int pick_streams(g3_dist* D, int lo, int hi, bool own_chain) {
   // bound and the reservation costs 7 %).  Where the rank's step is far longer than the chain (config 5's shape: 137 against
   // 59 ms) the reservation only costs, so a PLAN chooses (g3_dist_plan) between this stream and a plain one.  A CU-masked
   // stream cannot carry the low priority; it is still below the two high ones.
-  const int reserve = g3h_env_int("G3_DIST_BULK_MASK", D->world >= 6 ? 32 : 0);
+  int reserve = g3h_env_int("G3_DIST_BULK_MASK", D->world >= 6 ? 32 : 0);
   for (int i = 0; i < NLP && e == hipSuccess; ++i) e = hipStreamCreateWithPriority(&L[i], hipStreamNonBlocking, lo);
   if (reserve > 0) {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, D->ctx->device) != hipSuccess) e = hipErrorUnknown;
+    if (hipGetDeviceProperties(&prop, D->ctx->device) != hipSuccess) { cleanup(-1, -1, -1, -1); return G3_ERR_HIP; }
+    const int cus = prop.multiProcessorCount, words = (cus + 31) / 32;
     uint32_t mask[16];
-    for (int i = 0; i < 16; ++i) mask[i] = 0xffffffffu;
-    const uint32_t words = (uint32_t)((prop.multiProcessorCount + 31) / 32);
-    if (prop.multiProcessorCount % 32) mask[words - 1] = (1u << (prop.multiProcessorCount % 32)) - 1u;
-    for (int b = 0; b < reserve && b < prop.multiProcessorCount; ++b) mask[b / 32] &= ~(1u << (b % 32));
-    for (int i = NLP; i < NL && e == hipSuccess; ++i) e = hipExtStreamCreateWithCUMask(&L[i], words, mask);
+    if (words < 1 || words > 16) reserve = 0;          // a CU count whose mask does not fit: no masked stream
+    else {
+      for (int i = 0; i < 16; ++i) mask[i] = 0xffffffffu;
+      if (cus % 32) mask[words - 1] = (1u << (cus % 32)) - 1u;
+      for (int b = 0; b < reserve && b < cus; ++b) mask[b / 32] &= ~(1u << (b % 32));
+      for (int i = NLP; i < NL && e == hipSuccess; ++i) e = hipExtStreamCreateWithCUMask(&L[i], (uint32_t)words, mask);
+    }
   }
-  unsigned* scratch = nullptr;
   if (e == hipSuccess) e = hipMalloc((void**)&scratch, sizeof(unsigned));
-  auto cleanup = [&](int kc, int kl, int kb, int kb2) {
-    for (int i = 0; i < NH; ++i) if (H[i] && i != kc && i != kl) (void)hipStreamDestroy(H[i]);
-    for (int i = 0; i < NL; ++i) if (L[i] && i != kb && i != kb2) (void)hipStreamDestroy(L[i]);
-    if (scratch) (void)hipFree(scratch);
-  };
   if (e != hipSuccess) { cleanup(-1, -1, -1, -1); return G3_ERR_HIP; }
   int kc = 0, kl = 1, kb = 0, kbm = reserve > 0 ? NLP : -1;     // kb: the plain bulk stream; kbm: the masked one
   const bool probe = g3h_env_int("G3_DIST_PROBE", 1) != 0, log = g3h_env_int("G3_DIST_PROBE_LOG", 0) != 0;
-  hipStream_t user = D->ctx->stream;
   if (probe) {
-    // th[i][j]: latency of a one-wave kernel on high candidate i (index NH = the caller's stream) beside a dispatch-bound
-    // launch on low candidate j; tt[i][j]: the same beside one on high candidate j.  Two signatures: the SAME hardware
-    // queue (the small kernel waits for the whole launch: most of its duration), and two queues on the same compute
-    // PIPE (the pipe serves its queues in turns: ~100 us instead of ~35 for every dependent kernel of a chain)
-    double th[NH + 1][NL], tt[NH + 1][NH + 1], lmean = 0, base = 1e30;
-    bool hl[NH + 1][NL], hh[NH + 1][NH + 1];
+    // th[i][j]: latency of a one-wave kernel on high candidate i beside a dispatch-bound launch on low candidate j;
+    // tt[i][j]: the same beside one on high candidate j.  Two signatures: the SAME hardware queue (the small kernel waits
+    // for the whole launch: most of its duration), and two queues on the same compute PIPE (the pipe serves its queues in
+    // turns: ~100 us instead of ~35 for every dependent kernel of a chain)
+    double th[NH][NL], tt[NH][NH], lmean = 0, base = 1e30;
+    bool hl[NH][NL], hh[NH][NH];
     bool ok = true;
     double t_us = 0, l_us = 0;
     int nl = 0;
-    for (int i = 0; i <= NH && ok; ++i) {
-      hipStream_t a = i < NH ? H[i] : user;
+    for (int i = 0; i < NH && ok; ++i) {
       for (int j = 0; j < NL && ok; ++j) {
         if (!L[j]) { th[i][j] = 0; continue; }
-        ok = g3i_probe_pair(a, L[j], scratch, &t_us, &l_us, 2);
+        ok = g3i_probe_pair(H[i], L[j], scratch, &t_us, &l_us, 2);
         th[i][j] = t_us;
         lmean += l_us; ++nl;
         if (t_us < base) base = t_us;
       }
-      for (int j = 0; j <= NH && ok; ++j) {
+      for (int j = 0; j < NH && ok; ++j) {
         tt[i][j] = 0;
         if (j == i) continue;
-        hipStream_t b = j < NH ? H[j] : user;
-        ok = g3i_probe_pair(a, b, scratch, &t_us, &l_us, 1);
+        ok = g3i_probe_pair(H[i], H[j], scratch, &t_us, &l_us, 1);
         tt[i][j] = t_us;
         if (t_us < base) base = t_us;
       }
     }
     lmean /= nl > 0 ? nl : 1;
     const double limit = base * 2.0 > base + 40.0 ? base * 2.0 : base + 40.0;
-    for (int i = 0; i <= NH && ok; ++i) {
+    for (int i = 0; i < NH && ok; ++i) {
       for (int j = 0; j < NL; ++j) {
         hl[i][j] = L[j] != nullptr && th[i][j] > limit;
         if (log && L[j]) fprintf(stderr, "libg3hip placement: high %d / low %d: small kernel %.0f us beside a %.0f us dispatch-bound launch%s\n", i, j,
                          th[i][j], lmean, hl[i][j] ? (th[i][j] > 0.5 * lmean ? "  <- same queue" : "  <- same pipe") : "");
       }
-      for (int j = 0; j <= NH; ++j) {
+      for (int j = 0; j < NH; ++j) {
         hh[i][j] = j != i && tt[i][j] > limit;
         if (log && hh[i][j]) fprintf(stderr, "libg3hip placement: high %d / high %d: %.0f us%s\n", i, j, tt[i][j],
                                      tt[i][j] > 0.5 * lmean ? "  <- same queue" : "  <- same pipe");
       }
     }
     if (ok) {
-      // chain candidates: the driver's own (0 .. NH-1) or the caller's stream (NH); fewest conflicts wins, first in order on ties
-      // the two high streams together with the best plain AND the best masked bulk candidate for them: a plan may take either
+      // the two high streams together with the best plain AND the best masked bulk candidate for them (a plan may take either):
+      // fewest conflicts wins, first in order on ties
       int bestc = 1 << 30;
-      for (int c = own_chain ? 0 : NH; c <= (own_chain ? NH - 1 : NH); ++c)
+      for (int c = 0; c < NH; ++c)
         for (int l = 0; l < NH; ++l) {
           if (l == c) continue;
           int bp = 0, cp = 1 << 30, bm = -1, cm = 0;
@@ -791,12 +464,11 @@ static int pick_streams(g3_dist* D, int lo, int hi, bool own_chain) {
           const int conflicts = cp + cm + (int)(hh[c][l] || hh[l][c]);
           if (conflicts < bestc) { bestc = conflicts; kc = c; kl = l; kb = bp; kbm = bm; }
         }
-      if (log) fprintf(stderr, "libg3hip placement: chain = high %d%s, look-ahead = high %d, bulk = low %d, masked bulk = %d (%d conflicts)\n", kc,
-                       kc == NH ? " (caller's stream)" : "", kl, kb, kbm, bestc);
+      if (log) fprintf(stderr, "libg3hip placement: chain = high %d, look-ahead = high %d, bulk = low %d, masked bulk = %d (%d conflicts)\n", kc,
+                       kl, kb, kbm, bestc);
     }
   }
-  if (!own_chain) kc = NH;
-  D->s_chain = kc < NH ? H[kc] : nullptr;
+  D->s_chain = H[kc];
   D->s_look = H[kl];
   D->s_bulk_alt[0] = L[kb];
   D->s_bulk_alt[1] = kbm >= 0 ? L[kbm] : nullptr;
@@ -818,52 +490,32 @@ extern "C" int g3_dist_unique_id(void* id_out) {
   return G3_OK;
 }
 
-static int dist_common(g3_ctx* ctx, int rank, int world, g3_dist** out) {
-  g3_dist* D = new (std::nothrow) g3_dist();
-  if (!D) return G3_ERR_NOMEM;
+// what the four g3_dist_create* share: the driver object around a freshly allocated transport `t` (nullptr: out of memory),
+// which belongs to the driver from here on
+static int dist_common(g3_ctx* ctx, int rank, int world, Transport* t, g3_dist** out) {
+  g3_dist* D = t ? new (std::nothrow) g3_dist() : nullptr;
+  if (!D) { delete t; return G3_ERR_NOMEM; }
   D->ctx = ctx;
   D->rank = rank;
   D->world = world;
   g3_dev_guard _dg(ctx);
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = least priority, hi = greatest
-  // The driver's own two streams, and NOTHING else: the look-ahead and bulk contexts work on them and create no streams of
-  // their own.  HIP maps streams onto a few hardware queues per priority; with the four idle streams two ordinary contexts
-  // would bring, whether the chain stream and the look-ahead stream share a queue (and then serialise) depended on what
-  // else the process had created before (the same replay measured 45 or 37 ms at P = 8).
-  hipError_t e = hipSuccess;
-  for (int i = 0, n = g3h_env_int("G3_DIST_PAD_STREAMS", 0); i < n && e == hipSuccess; ++i) {
-    hipStream_t ps = nullptr;
-    e = hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, (i & 1) ? lo : hi);
-    if (e == hipSuccess) D->pad_streams.push_back(ps);
-  }
-  const bool own_chain = g3h_env_int("G3_DIST_OWN_CHAIN", 1) != 0;
-  if (e == hipSuccess && pick_streams(D, lo, hi, own_chain) != G3_OK) e = hipErrorUnknown;
-  if (e == hipSuccess && D->s_chain) e = hipEventCreateWithFlags(&D->ev_bracket, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc((void**)&D->info_dev, sizeof(int));
-  int rc = e == hipSuccess ? G3_OK : G3_ERR_HIP;
+  // The streams pick_streams keeps are the only ones the driver holds: the look-ahead and bulk contexts are created ON them
+  // (g3i_ctx_create_on) and bring no streams of their own.  HIP maps streams onto a few hardware queues per priority, and
+  // every idle stream more shifts which queues the three of the sweep land on (the same replay measured 45 or 37 ms at P = 8).
+  int rc = pick_streams(D, lo, hi);
+  if (rc) { delete D; delete t; return rc; }         // (nothing else exists yet)
+  D->tr = t;
+  if (hipEventCreateWithFlags(&D->ev_bracket, hipEventDisableTiming) != hipSuccess || hipMalloc((void**)&D->info_dev, sizeof(int)) != hipSuccess)
+    rc = G3_ERR_HIP;
   if (!rc) rc = g3i_ctx_create_on(ctx->device, D->s_look, &D->ctx_look);
   for (int i = 0; i < 2 && !rc; ++i)
     if (D->s_bulk_alt[i]) rc = g3i_ctx_create_on(ctx->device, D->s_bulk_alt[i], &D->ctx_bulk_alt[i]);
   D->ctx_bulk = D->ctx_bulk_alt[0];
-  if (rc) {
-    if (D->ctx_look) g3_ctx_destroy(D->ctx_look);
-    for (int i = 0; i < 2; ++i) if (D->ctx_bulk_alt[i]) g3_ctx_destroy(D->ctx_bulk_alt[i]);
-    if (D->s_look) (void)hipStreamDestroy(D->s_look);
-    for (int i = 0; i < 2; ++i) if (D->s_bulk_alt[i]) (void)hipStreamDestroy(D->s_bulk_alt[i]);
-    if (D->s_chain) (void)hipStreamDestroy(D->s_chain);
-    if (D->ev_bracket) (void)hipEventDestroy(D->ev_bracket);
-    for (hipStream_t ps : D->pad_streams) (void)hipStreamDestroy(ps);
-    if (D->info_dev) (void)hipFree(D->info_dev);
-    delete D;
-    return rc;
-  }
+  if (rc) { g3_dist_destroy(D); return rc; }         // the three streams exist: an ordinary teardown
   D->serial_coll = g3h_env_int("G3_DIST_SERIAL_COLL", 0) != 0;
   D->want_fullinv = g3h_env_int("G3_DIST_FULLINV", 1) != 0;
-  {
-    const char* dl = getenv("G3_DIST_DEAL");
-    D->deal_snake = (dl && !strcmp(dl, "snake")) ? 1 : 0;
-  }
   for (int i = 0; i < 2; ++i)
     if (D->ctx_bulk_alt[i]) D->ctx_bulk_alt[i]->bulk_role = true;     // its small-tile launches leave room on every CU for the chain's kernels (g3_gemm.hip)
   {
@@ -872,6 +524,11 @@ static int dist_common(g3_ctx* ctx, int rank, int world, g3_dist** out) {
   }
   *out = D;
   return G3_OK;
+}
+// rc: how bringing the transport up went; a driver whose transport failed is destroyed
+static int dist_started(g3_dist** out, int rc) {
+  if (rc) { g3_dist_destroy(*out); *out = nullptr; }
+  return rc;
 }
 
 extern "C" int g3_dist_create(g3_ctx* ctx, const void* id_gather, const void* id_bcast, int rank, int world, g3_dist** out) {
@@ -883,14 +540,11 @@ extern "C" int g3_dist_create(g3_ctx* ctx, const void* id_gather, const void* id
   *out = nullptr;
   RcclApi* api = rccl_api(ctx->err, sizeof(ctx->err));
   if (!api) return G3_ERR_HIP;
-  g3_dist* D = nullptr;
-  int rc = dist_common(ctx, rank, world, &D);
+  RcclTransport* t = new (std::nothrow) RcclTransport();
+  if (t) t->api = api;
+  int rc = dist_common(ctx, rank, world, t, out);
   if (rc) return rc;
   g3_dev_guard _dg(ctx);
-  RcclTransport* t = new (std::nothrow) RcclTransport();
-  if (!t) { g3_dist_destroy(D); return G3_ERR_NOMEM; }
-  t->api = api;
-  D->tr = t;
   ncclUniqueId a, b;
   memcpy(&a, id_gather, sizeof(a));
   memcpy(&b, id_bcast, sizeof(b));
@@ -900,16 +554,12 @@ extern "C" int g3_dist_create(g3_ctx* ctx, const void* id_gather, const void* id
   if (r == ncclSuccess) r = api->CommInitRank(&t->comm_bcast, world, b, rank);
   if (r != ncclSuccess) {
     snprintf(ctx->err, sizeof(ctx->err), "ncclCommInitRank: %s", api->GetErrorString(r));
-    g3_dist_destroy(D);
-    return G3_ERR_HIP;
+    rc = G3_ERR_HIP;
+  } else if (hipMalloc((void**)&t->scratch, RcclTransport::SCR * sizeof(double)) != hipSuccess ||
+             hipHostMalloc((void**)&t->hscratch, RcclTransport::SCR * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+    rc = G3_ERR_HIP;
   }
-  if (hipMalloc((void**)&t->scratch, RcclTransport::SCR * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&t->hscratch, RcclTransport::SCR * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-    g3_dist_destroy(D);
-    return G3_ERR_HIP;
-  }
-  *out = D;
-  return G3_OK;
+  return dist_started(out, rc);
 }
 
 extern "C" int g3_dist_create_callbacks(g3_ctx* ctx, const g3_dist_callbacks* cb, int rank, int world, g3_dist** out) {
@@ -918,15 +568,9 @@ extern "C" int g3_dist_create_callbacks(g3_ctx* ctx, const g3_dist_callbacks* cb
   if (world < 1 || rank < 0 || rank >= world) return -3;
   if (!out) return -5;
   *out = nullptr;
-  g3_dist* D = nullptr;
-  int rc = dist_common(ctx, rank, world, &D);
-  if (rc) return rc;
   CallbackTransport* t = new (std::nothrow) CallbackTransport();
-  if (!t) { g3_dist_destroy(D); return G3_ERR_NOMEM; }
-  t->cb = *cb;
-  D->tr = t;
-  *out = D;
-  return G3_OK;
+  if (t) t->cb = *cb;
+  return dist_common(ctx, rank, world, t, out);
 }
 
 extern "C" int g3_dist_create_callbacks_async(g3_ctx* ctx, const g3_dist_host_callbacks* cb, int rank, int world, g3_dist** out) {
@@ -935,21 +579,17 @@ extern "C" int g3_dist_create_callbacks_async(g3_ctx* ctx, const g3_dist_host_ca
   if (world < 1 || rank < 0 || rank >= world) return -3;
   if (!out) return -5;
   *out = nullptr;
-  g3_dist* D = nullptr;
-  int rc = dist_common(ctx, rank, world, &D);
+  AsyncCallbackTransport* t = new (std::nothrow) AsyncCallbackTransport();
+  if (t) {
+    t->cb = *cb;
+    t->device = ctx->device;
+    t->rank = rank;
+    t->world = world;
+  }
+  int rc = dist_common(ctx, rank, world, t, out);
   if (rc) return rc;
   g3_dev_guard _dg(ctx);
-  AsyncCallbackTransport* t = new (std::nothrow) AsyncCallbackTransport();
-  if (!t) { g3_dist_destroy(D); return G3_ERR_NOMEM; }
-  t->cb = *cb;
-  t->device = ctx->device;
-  t->rank = rank;
-  t->world = world;
-  D->tr = t;
-  rc = t->start();
-  if (rc) { g3_dist_destroy(D); return rc; }
-  *out = D;
-  return G3_OK;
+  return dist_started(out, t->start());
 }
 
 extern "C" int g3_dist_set_keep(g3_dist* D, int on) {
@@ -969,28 +609,24 @@ extern "C" int g3_dist_create_replay(g3_ctx* ctx, g3_dist* reference, int rank, 
   if (world < 1 || rank < 0 || rank >= world) return -3;
   if (!out) return -5;
   *out = nullptr;
-  g3_dist* D = nullptr;
-  int rc = dist_common(ctx, rank, world, &D);
-  if (rc) return rc;
   ReplayTransport* t = new (std::nothrow) ReplayTransport();
-  if (!t) { g3_dist_destroy(D); return G3_ERR_NOMEM; }
-  t->self = D;
+  int rc = dist_common(ctx, rank, world, t, out);
+  if (rc) return rc;
+  t->self = *out;
   t->ref = reference;
   reference->replay_refs += 1;       // released by g3_dist_destroy of the replay
-  D->want_fullinv = reference->fullinv;   // the replayed rank must run the schedule the reference ran
-  D->tr = t;
-  *out = D;
+  (*out)->want_fullinv = reference->fullinv;   // the replayed rank must run the schedule the reference ran
   return G3_OK;
 }
 
 static void free_plan(g3_dist* D) {
-  void* bufs[] = {D->A, D->dbuf[0], D->dbuf[1], D->send[0], D->send[1], D->gath[0], D->gath[1], D->gath[2], D->avec, D->dots,
-                  D->Kinv, D->alpha_dev, D->agath, D->wstore, D->blkstats, D->vstore, D->vt, D->ubuf, D->rbuf};
+  void* bufs[] = {D->A, D->dbuf[0], D->dbuf[1], D->gath[0], D->gath[1], D->gath[2], D->avec, D->dots,
+                  D->Kinv, D->alpha_dev, D->agath, D->asend, D->wstore, D->blkstats, D->vstore, D->vt, D->ubuf, D->rbuf};
   D->blkstats = nullptr;
   D->vstore = D->vt = D->ubuf = D->rbuf = nullptr;
   for (void* b : bufs) if (b) (void)hipFree(b);
-  D->A = D->dbuf[0] = D->dbuf[1] = D->send[0] = D->send[1] = D->gath[0] = D->gath[1] = D->gath[2] = D->avec = D->dots = nullptr;
-  D->Kinv = D->alpha_dev = D->agath = nullptr;
+  D->A = D->dbuf[0] = D->dbuf[1] = D->gath[0] = D->gath[1] = D->gath[2] = D->avec = D->dots = nullptr;
+  D->Kinv = D->alpha_dev = D->agath = D->asend = nullptr;
   D->wstore = nullptr;
   D->have_inv = false;
   for (hipEvent_t e : D->ev) (void)hipEventDestroy(e);
@@ -1018,13 +654,10 @@ extern "C" int g3_dist_destroy(g3_dist* D) {
   for (int i = 0; i < 2; ++i) if (D->ctx_bulk_alt[i]) g3_ctx_destroy(D->ctx_bulk_alt[i]);
   if (D->s_look) (void)hipStreamDestroy(D->s_look);
   for (int i = 0; i < 2; ++i) if (D->s_bulk_alt[i]) (void)hipStreamDestroy(D->s_bulk_alt[i]);
-  if (D->s_chain) {
-    (void)hipStreamSynchronize(D->s_chain);
-    g3i_ctx_forget_stream(D->ctx, D->s_chain);      // the caller's context worked on it inside every entry point
-    (void)hipStreamDestroy(D->s_chain);
-  }
+  (void)hipStreamSynchronize(D->s_chain);
+  g3i_ctx_forget_stream(D->ctx, D->s_chain);        // the caller's context worked on it inside every entry point
+  (void)hipStreamDestroy(D->s_chain);
   if (D->ev_bracket) (void)hipEventDestroy(D->ev_bracket);
-  for (hipStream_t ps : D->pad_streams) (void)hipStreamDestroy(ps);
   delete D;
   return G3_OK;
 }
@@ -1065,7 +698,7 @@ extern "C" int g3_dist_plan(g3_dist* D, int64_t N, int d, int64_t M, int64_t nb,
   D->Mp = g3_roundup(M, 128);
   D->nchunk = 1 + (int)(D->Mp / 128);
   D->my_blocks.clear(); D->my_chunks.clear();
-  g3h_deal(D->world, D->nblk, &D->owner, D->deal_snake);
+  g3h_deal(D->world, D->nblk, &D->owner);
   D->loff.assign(D->nblk, -1);
   for (int I = 0; I < D->nblk; ++I)
     if (owner_of(D, I) == D->rank) { D->loff[I] = (int64_t)D->my_blocks.size() * nb; D->my_blocks.push_back(I); }
@@ -1090,8 +723,6 @@ extern "C" int g3_dist_plan(g3_dist* D, int64_t N, int d, int64_t M, int64_t nb,
     G3D_HIP(hipMalloc((void**)&D->dbuf[i], dbuf_bytes(D)));
     // (the blocks of V above the block diagonal are never written: keep them zero for whoever reads V densely)
     G3D_HIP(hipMemsetAsync(D->dbuf[i], 0, dbuf_bytes(D), D->ctx->stream));
-    G3D_HIP(hipMalloc((void**)&D->send[i], (size_t)D->cmax * nb * nb * D->es));
-    G3D_HIP(hipMemsetAsync(D->send[i], 0, (size_t)D->cmax * nb * nb * D->es, D->ctx->stream));
   }
   // three gather buffers: the bulk update with panel k may still be reading its buffer while panel k + 2 arrives
   for (int i = 0; i < 3; ++i) {
@@ -1116,6 +747,7 @@ extern "C" int g3_dist_plan(g3_dist* D, int64_t N, int d, int64_t M, int64_t nb,
     G3D_HIP(hipMalloc((void**)&D->Kinv, (size_t)(D->rows_mat ? D->rows_mat : 1) * D->Np * D->es));
     G3D_HIP(hipMalloc((void**)&D->alpha_dev, (size_t)D->Np * D->es));
     G3D_HIP(hipMalloc((void**)&D->agath, (size_t)D->world * D->cmax_all * nb * D->es));
+    G3D_HIP(hipMalloc((void**)&D->asend, (size_t)D->cmax_all * nb * D->es));
   }
   if (ReplayTransport* rt = dynamic_cast<ReplayTransport*>(D->tr)) {
     if (rt->ref->Np != D->Np || rt->ref->nb != D->nb || rt->ref->dt != D->dt || rt->ref->M != D->M || D->grad ||
@@ -1168,7 +800,7 @@ static int build(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel_prog* p
     for (int I : D->my_blocks) {
       G3D_RC(D->ctx, g3_gram_rows(D->ctx, prog, X, D->N, ldx, D->d, (int64_t)I * nb, nb, D->dt, Aat(D, D->loff[I], 0), D->Np,
                                   G3_GRAM_SCRUB | G3_GRAM_PAD_EYE));
-      const int64_t nv = D->N - (int64_t)I * nb < nb ? D->N - (int64_t)I * nb : nb;
+      const int64_t nv = valid_rows(D, I);
       if (nv > 0) {
         G3D_RC(D->ctx, g3i_diag_stats_dev(D->ctx, Aat(D, D->loff[I], (int64_t)I * nb), nv, D->Np, D->dt, D->blkstats + 4 * cnt));
         ++cnt;
@@ -1188,8 +820,10 @@ static int build(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel_prog* p
   }
   if (D->rows_inv > 0) {     // the identity, row block I of it stored like block I of the matrix
     G3D_HIP(hipMemsetAsync(Aat(D, D->rows_mat + D->rows_rhs, 0), 0, (size_t)D->rows_inv * D->Np * D->es, D->ctx->stream));
-    for (int I : D->my_blocks)
-      G3D_RC(D->ctx, g3_diag_add(D->ctx, Aat(D, D->rows_mat + D->rows_rhs + D->loff[I], (int64_t)I * nb), nb, D->Np, D->dt, 1.0));
+    for (int I : D->my_blocks) {
+      int rc = set_block_diag(D, D->rows_mat + D->rows_rhs, I, 1.0, true);
+      if (rc) return rc;
+    }
   }
   // tt_to_cov (tensors.py:95-98): min over the WHOLE diagonal
   double g = isfinite(lmin) ? lmin : 1e300;
@@ -1199,7 +833,7 @@ static int build(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel_prog* p
   if (!(g > 0)) add += (double)1e-6f - g;
   if (add != 0.0)
     for (int I : D->my_blocks) {
-      const int64_t nv = D->N - (int64_t)I * nb < nb ? D->N - (int64_t)I * nb : nb;
+      const int64_t nv = valid_rows(D, I);
       if (nv > 0) G3D_RC(D->ctx, g3_diag_add(D->ctx, Aat(D, D->loff[I], (int64_t)I * nb), nv, D->Np, D->dt, add));
     }
   return G3_OK;
@@ -1353,9 +987,16 @@ static int stair(g3_dist* D, g3_ctx* cx, int64_t row0, int64_t col0, int64_t kco
   return stair_ptr(D, cx, Aat(D, row0, col0), Aat(D, row0, kcol), D->Np, G, seg_rows, seg_cols, perm, nperm, seg_diag, -1.0);
 }
 
+// one of the three staircase launches of step k (g3h_step_segments, g3_host.h), with the gathered panel k
+static int step_stair(g3_dist* D, g3_ctx* cx, int k, int64_t rr, G3hStep which, const std::vector<int32_t>& perm) {
+  const G3hStepSegments sg = g3h_step_segments(D->my_blocks, D->loff, D->nb, D->nblk, D->rows_mat, rr, k, which);
+  if (sg.rows.empty()) return G3_OK;
+  return stair(D, cx, sg.lo, (int64_t)(k + 1 + sg.blk0) * D->nb, (int64_t)k * D->nb, D->gath[k % 3], sg.rows, sg.cols, perm.data() + sg.blk0,
+               sg.nblk, which == G3H_STEP_A ? nullptr : &sg.diag);
+}
+
 static int factor(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel_prog* prog_cross, const void* X, int64_t ldx, const void* Xs,
                   int64_t ldxs, const void* delta, double jitter, int* info_out) {
-  const int64_t nb = D->nb;
   const int nblk = D->nblk;
   hipStream_t sA = D->ctx->stream, sB = D->s_bulk;
   hipEvent_t ev_tmp = D->ev[nblk], ev_join = D->ev[nblk + 1], ev_bc[2] = {D->ev[nblk + 2], D->ev[nblk + 3]}, ev_sv = D->ev[nblk + 4];
@@ -1378,11 +1019,8 @@ static int factor(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel_prog* 
   }
   hipEvent_t ev_prev = nullptr;
   std::vector<int32_t> perm;
-  std::vector<int64_t> seg_rows, seg_cols, seg_diag;
   for (int k = 0; k + 1 < nblk; ++k) {
-    const int64_t c0 = (int64_t)k * nb, c1 = c0 + nb, c2 = c1 + nb, c3 = c2 + nb;
     perm_of(D, k, &perm);
-    const char* G = D->gath[k % 3];
     hipEvent_t ev_k = nullptr;
     const int64_t rr = D->rows_rhs + inv_active(D, k);     // right-hand-side rows panel k applies to
     // ---- bulk stream: everything beyond block column k+1 (after the gather of panel k, queued on the chain)
@@ -1390,38 +1028,18 @@ static int factor(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel_prog* 
     if (rc) return rc;
     if (k + 2 < nblk) {
       // d1. block column k+2 (block k+2's diagonal block included: the look-ahead adds panel k+1 only)
-      seg_rows.clear(); seg_cols.clear(); seg_diag.clear();
-      int64_t lo = -1;
-      for (int I : D->my_blocks) if (I >= k + 2) { if (lo < 0) lo = D->loff[I]; seg_rows.push_back(nb); seg_cols.push_back(nb); seg_diag.push_back(I == k + 2); }
-      if (rr > 0) { if (lo < 0) lo = D->rows_mat; seg_rows.push_back(rr); seg_cols.push_back(nb); seg_diag.push_back(0); }
-      if (!seg_rows.empty()) {
-        rc = stair(D, D->ctx_bulk, lo, c2, c0, G, seg_rows, seg_cols, perm.data() + 1, 1, &seg_diag);
-        if (rc) return rc;
-      }
+      rc = step_stair(D, D->ctx_bulk, k, rr, G3H_STEP_D1, perm);
+      if (rc) return rc;
       ev_k = D->ev[k];
       G3D_HIP(hipEventRecord(ev_k, sB));
       // d2. the rest: block columns >= k+3 of my blocks >= k+3 and of the right-hand-side rows
-      seg_rows.clear(); seg_cols.clear(); seg_diag.clear();
-      lo = -1;
-      for (int I : D->my_blocks) if (I >= k + 3) { if (lo < 0) lo = D->loff[I]; seg_rows.push_back(nb); seg_cols.push_back((int64_t)(I - k - 2) * nb); seg_diag.push_back(1); }
-      if (rr > 0 && nblk - k - 3 > 0) { if (lo < 0) lo = D->rows_mat; seg_rows.push_back(rr); seg_cols.push_back((int64_t)(nblk - k - 3) * nb); seg_diag.push_back(0); }
-      if (!seg_rows.empty()) {
-        rc = stair(D, D->ctx_bulk, lo, c3, c0, G, seg_rows, seg_cols, perm.data() + 2, (int)perm.size() - 2, &seg_diag);
-        if (rc) return rc;
-      }
+      rc = step_stair(D, D->ctx_bulk, k, rr, G3H_STEP_D2, perm);
+      if (rc) return rc;
     }
     // ---- chain: a. block column k+1 (it carries the updates up to panel k-1 once B_{k-1} has fired)
     if (ev_prev) G3D_HIP(hipStreamWaitEvent(sA, ev_prev, 0));
-    {
-      seg_rows.clear(); seg_cols.clear();
-      int64_t lo = -1;
-      for (int I : D->my_blocks) if (I >= k + 2) { if (lo < 0) lo = D->loff[I]; seg_rows.push_back(nb); seg_cols.push_back(nb); }
-      if (rr > 0) { if (lo < 0) lo = D->rows_mat; seg_rows.push_back(rr); seg_cols.push_back(nb); }
-      if (!seg_rows.empty()) {
-        rc = stair(D, D->ctx, lo, c1, c0, G, seg_rows, seg_cols, perm.data(), 1);
-        if (rc) return rc;
-      }
-    }
+    rc = step_stair(D, D->ctx, k, rr, G3H_STEP_A, perm);
+    if (rc) return rc;
     // b. panel k+1: needs the broadcast factor
     G3D_HIP(hipStreamWaitEvent(sA, ev_bc[(k + 1) % 2], 0));
     rc = solve_and_gather(D, k + 1, ev_sv);
@@ -1461,7 +1079,7 @@ static int factor_robust(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel
     if (rc) return rc;
     double acc[2] = {0.0, 0.0}, mn = INFINITY;
     for (int I : D->my_blocks) {
-      const int64_t nv = D->N - (int64_t)I * D->nb < D->nb ? D->N - (int64_t)I * D->nb : D->nb;
+      const int64_t nv = valid_rows(D, I);
       if (nv > 0) {
         double st[3];
         G3D_RC(D->ctx, g3_diag_stats(D->ctx, Aat(D, D->loff[I], (int64_t)I * D->nb), nv, D->Np, D->dt, st));
@@ -1493,11 +1111,8 @@ static int factor_robust(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel
       const double c = (double)1e-10f;
       if (D->rows_mat > 0) G3D_HIP(hipMemsetAsync(D->A, 0, (size_t)D->rows_mat * D->Np * D->es, D->ctx->stream));
       for (int I : D->my_blocks) {
-        const int64_t nv0 = D->N - (int64_t)I * D->nb;
-        const int64_t nv = nv0 < 0 ? 0 : (nv0 < D->nb ? nv0 : D->nb);
-        char* Dg = Aat(D, D->loff[I], (int64_t)I * D->nb);
-        if (nv > 0) G3D_RC(D->ctx, g3_diag_add(D->ctx, Dg, nv, D->Np, D->dt, c));
-        if (nv < D->nb) G3D_RC(D->ctx, g3_diag_add(D->ctx, Dg + ((size_t)nv * D->Np + nv) * D->es, D->nb - nv, D->Np, D->dt, 1.0));
+        rc = set_block_diag(D, 0, I, c);
+        if (rc) return rc;
       }
       for (size_t t = 0; t < D->my_chunks.size(); ++t) {
         rc = rhs_rows(D, (int)t, D->my_chunks[t], prog_cross, X, ldx, Xs, ldxs, delta);
@@ -1508,11 +1123,8 @@ static int factor_robust(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel
       if (D->rows_inv > 0) {     // L^-T of the fallback factor: 1e10 on the valid diagonal, 1 on the padding
         G3D_HIP(hipMemsetAsync(Aat(D, D->rows_mat + D->rows_rhs, 0), 0, (size_t)D->rows_inv * D->Np * D->es, D->ctx->stream));
         for (int I : D->my_blocks) {
-          const int64_t nv0 = D->N - (int64_t)I * D->nb;
-          const int64_t nv = nv0 < 0 ? 0 : (nv0 < D->nb ? nv0 : D->nb);
-          char* Dg = Aat(D, D->rows_mat + D->rows_rhs + D->loff[I], (int64_t)I * D->nb);
-          if (nv > 0) G3D_RC(D->ctx, g3_diag_add(D->ctx, Dg, nv, D->Np, D->dt, 1.0 / c));
-          if (nv < D->nb) G3D_RC(D->ctx, g3_diag_add(D->ctx, Dg + ((size_t)nv * D->Np + nv) * D->es, D->nb - nv, D->Np, D->dt, 1.0));
+          rc = set_block_diag(D, D->rows_mat + D->rows_rhs, I, 1.0 / c);
+          if (rc) return rc;
         }
       }
     }
@@ -1526,14 +1138,13 @@ static int factor_robust(g3_dist* D, const g3_kernel_prog* prog, const g3_kernel
 
 // (logdet, quad, mean pieces[M], ss[M]) summed over all ranks
 static int stats(g3_dist* D, double* logdet, double* quad, double* mean, double* ss) {
-  const int64_t nb = D->nb, M = D->M, Np = D->Np;
+  const int64_t M = D->M, Np = D->Np;
   std::vector<double> acc(2 + 2 * M, 0.0);
   int nstat = 0;
   for (int I : D->my_blocks) {
-    const int64_t nv0 = D->N - (int64_t)I * nb;
-    const int64_t nv = nv0 < 0 ? 0 : (nv0 < nb ? nv0 : nb);
+    const int64_t nv = valid_rows(D, I);
     if (nv > 0) {
-      G3D_RC(D->ctx, g3i_logp_terms_dev(D->ctx, Aat(D, D->loff[I], (int64_t)I * nb), nv, Np, nullptr, D->dt, D->blkstats + 4 * nstat));
+      G3D_RC(D->ctx, g3i_logp_terms_dev(D->ctx, Aat(D, D->loff[I], (int64_t)I * D->nb), nv, Np, nullptr, D->dt, D->blkstats + 4 * nstat));
       ++nstat;
     }
   }
@@ -1551,7 +1162,7 @@ static int stats(g3_dist* D, double* logdet, double* quad, double* mean, double*
     G3D_HIP(hipStreamSynchronize(D->ctx->stream));
     double q = 0.0;
     for (int64_t i = 0; i < Np; ++i) {
-      const double v = D->dt == G3_F64 ? ((const double*)ha.data())[i] : (double)((const float*)ha.data())[i];
+      const double v = host_at(D, ha.data(), (size_t)i);
       q += v * v;
     }
     acc[1] = q;
@@ -1579,13 +1190,8 @@ static int stats(g3_dist* D, double* logdet, double* quad, double* mean, double*
     const int64_t m = M - s0 < 128 ? M - s0 : 128;
     const char* h = hb.data() + t * pair;
     for (int64_t i = 0; i < m; ++i) {
-      if (D->dt == G3_F64) {
-        acc[2 + s0 + i] += ((const double*)h)[i];
-        acc[2 + M + s0 + i] += ((const double*)h)[128 + i];
-      } else {
-        acc[2 + s0 + i] += (double)((const float*)h)[i];
-        acc[2 + M + s0 + i] += (double)((const float*)h)[128 + i];
-      }
+      acc[2 + s0 + i] += host_at(D, h, (size_t)i);
+      acc[2 + M + s0 + i] += host_at(D, h, (size_t)(128 + i));
     }
   }
   rc = do_allreduce(D, acc.data(), (int)acc.size(), 0);
@@ -1667,6 +1273,20 @@ __global__ void __launch_bounds__(256) mirror_lower_kernel(T* __restrict__ A, in
   if (j < n && j > i) A[i * ld + j] = A[j * ld + i];
 }
 
+// a device temporary of one entry point: freed when the scope ends, once the stream that may still read it has drained
+struct DevTmp {
+  hipStream_t s;
+  char* p = nullptr;
+  explicit DevTmp(hipStream_t s_) : s(s_) {}
+  ~DevTmp() {
+    if (!p) return;
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(p);
+  }
+  DevTmp(const DevTmp&) = delete;
+  DevTmp& operator=(const DevTmp&) = delete;
+};
+
 static int posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_dev, int64_t ldxs, char* cov, int64_t ldc) {
   const int P = D->world;
   const int64_t M = D->M, Mp = D->Mp, Np = D->Np, pad = 128;
@@ -1676,35 +1296,28 @@ static int posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_
   int cmax = 1;
   for (int q = 0; q < P; ++q) cmax = cntq[q] > cmax ? cntq[q] : cmax;
   hipStream_t s = D->ctx->stream;
-  char *sendb = nullptr, *Vall = nullptr, *rows = nullptr, *call = nullptr;
-  int rc = G3_OK;
-  auto cleanup = [&]() {
-    void* b[] = {sendb, Vall, rows, call};
-    (void)hipStreamSynchronize(s);
-    for (void* p : b) if (p) (void)hipFree(p);
-  };
-#define G3D_TRY(x) do { rc = (x); if (rc) { cleanup(); return rc; } } while (0)
-#define G3D_TRYH(x) do { if ((x) != hipSuccess) { snprintf(D->err, sizeof(D->err), "%s:%d %s", __FILE__, __LINE__, #x); cleanup(); return G3_ERR_HIP; } } while (0)
+  DevTmp t_send(s), t_vall(s), t_rows(s), t_call(s);
   const size_t es = D->es;
-  G3D_TRYH(hipMalloc((void**)&sendb, (size_t)cmax * pad * Np * es));
-  G3D_TRYH(hipMalloc((void**)&Vall, (size_t)P * cmax * pad * Np * es));
-  G3D_TRYH(hipMalloc((void**)&rows, (size_t)cmax * pad * Mp * es));
-  G3D_TRYH(hipMalloc((void**)&call, (size_t)P * cmax * pad * Mp * es));
-  G3D_TRYH(hipMemsetAsync(sendb, 0, (size_t)cmax * pad * Np * es, s));
-  G3D_TRYH(hipMemsetAsync(rows, 0, (size_t)cmax * pad * Mp * es, s));
+  G3D_HIP(hipMalloc((void**)&t_send.p, (size_t)cmax * pad * Np * es));
+  G3D_HIP(hipMalloc((void**)&t_vall.p, (size_t)P * cmax * pad * Np * es));
+  G3D_HIP(hipMalloc((void**)&t_rows.p, (size_t)cmax * pad * Mp * es));
+  G3D_HIP(hipMalloc((void**)&t_call.p, (size_t)P * cmax * pad * Mp * es));
+  char *sendb = t_send.p, *Vall = t_vall.p, *rows = t_rows.p, *call = t_call.p;
+  G3D_HIP(hipMemsetAsync(sendb, 0, (size_t)cmax * pad * Np * es, s));
+  G3D_HIP(hipMemsetAsync(rows, 0, (size_t)cmax * pad * Mp * es, s));
   // my V chunks, in chunk order (chunk c of Xs = right-hand-side chunk c + 1)
   for (size_t i = 0; i < mine.size(); ++i) {
     size_t t = 0;
     while (t < D->my_chunks.size() && D->my_chunks[t] != mine[i] + 1) ++t;
     if (t == D->my_chunks.size()) {     // the two dealings (plan: c % P; here: (c + 1) % P of the Xs chunk) must agree
       snprintf(D->err, sizeof(D->err), "posterior covariance: right-hand-side chunk %d is not on rank %d", mine[i] + 1, D->rank);
-      cleanup();
       return G3_ERR_HIP;
     }
-    G3D_TRYH(hipMemcpyAsync(sendb + i * pad * Np * es, Aat(D, D->rows_mat + (int64_t)t * pad, 0), (size_t)pad * Np * es,
-                            hipMemcpyDeviceToDevice, s));
+    G3D_HIP(hipMemcpyAsync(sendb + i * pad * Np * es, Aat(D, D->rows_mat + (int64_t)t * pad, 0), (size_t)pad * Np * es,
+                           hipMemcpyDeviceToDevice, s));
   }
-  G3D_TRY(do_allgather(D, sendb, Vall, (size_t)cmax * pad * Np * es, s));
+  int rc = do_allgather(D, sendb, Vall, (size_t)cmax * pad * Np * es, s);
+  if (rc) return rc;
   std::vector<int32_t> perm(nch);
   {
     std::vector<int> seen(P, 0);
@@ -1717,7 +1330,7 @@ static int posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_
     const int64_t c = mine[i];
     const int64_t m = M - c * pad < pad ? M - c * pad : pad;
     if (m > 0)
-      G3D_TRY(g3_gram_rows(D->ctx, prog, Xs_dev, M, ldxs, D->d, c * pad, m, D->dt, rows + i * pad * Mp * es, Mp, 0));
+      G3D_RC(D->ctx, g3_gram_rows(D->ctx, prog, Xs_dev, M, ldxs, D->d, c * pad, m, D->dt, rows + i * pad * Mp * es, Mp, 0));
     sr.push_back(pad);
     sc.push_back((c + 1) * pad);
     sd.push_back(1);
@@ -1726,23 +1339,20 @@ static int posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_
     std::vector<G3hStairChunk> ch;
     g3h_stair_chunks(sr, sc, pad, nch, &ch, &sd, D->ctx->tune.stair_max);
     for (const auto& cc : ch)
-      G3D_TRY(g3_gemm_nt_stair(D->ctx, rows + ((size_t)cc.row0 * Mp + cc.col0) * es, Mp, sendb + (size_t)cc.row0 * Np * es, Np, Vall, Np, Np,
-                               cc.rows.data(), cc.cols.data(), (int)cc.rows.size(), -1.0, 1.0, D->dt, pad, perm.data() + cc.blk0, cc.nblk,
-                               cc.diag.data()));
+      G3D_RC(D->ctx, g3_gemm_nt_stair(D->ctx, rows + ((size_t)cc.row0 * Mp + cc.col0) * es, Mp, sendb + (size_t)cc.row0 * Np * es, Np, Vall, Np,
+                                      Np, cc.rows.data(), cc.cols.data(), (int)cc.rows.size(), -1.0, 1.0, D->dt, pad, perm.data() + cc.blk0,
+                                      cc.nblk, cc.diag.data()));
   }
-  G3D_TRY(do_allgather(D, rows, call, (size_t)cmax * pad * Mp * es, s));
+  rc = do_allgather(D, rows, call, (size_t)cmax * pad * Mp * es, s);
+  if (rc) return rc;
   for (int c = 0; c < nch; ++c)
-    G3D_TRYH(hipMemcpy2DAsync(cov + (size_t)c * pad * ldc * es, (size_t)ldc * es, call + (size_t)perm[c] * pad * Mp * es, (size_t)Mp * es,
-                              (size_t)Mp * es, pad, hipMemcpyDeviceToDevice, s));
-  {
-    const dim3 grid((unsigned)((Mp + 255) / 256), (unsigned)Mp);
-    if (D->dt == G3_F64) hipLaunchKernelGGL(mirror_lower_kernel<double>, grid, dim3(256), 0, s, (double*)cov, Mp, ldc);
-    else hipLaunchKernelGGL(mirror_lower_kernel<float>, grid, dim3(256), 0, s, (float*)cov, Mp, ldc);
-    G3D_TRYH(hipGetLastError());
-  }
-  cleanup();
-#undef G3D_TRY
-#undef G3D_TRYH
+    G3D_HIP(hipMemcpy2DAsync(cov + (size_t)c * pad * ldc * es, (size_t)ldc * es, call + (size_t)perm[c] * pad * Mp * es, (size_t)Mp * es,
+                             (size_t)Mp * es, pad, hipMemcpyDeviceToDevice, s));
+  by_dtype(D, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(mirror_lower_kernel<T>, dim3((unsigned)((Mp + 255) / 256), (unsigned)Mp), dim3(256), 0, s, (T*)cov, Mp, ldc);
+  });
+  G3D_HIP(hipGetLastError());
   return G3_OK;
 }
 
@@ -1783,18 +1393,13 @@ extern "C" int g3_dist_posterior_draws(g3_dist* D, const g3_kernel_prog* prog_f,
   const int64_t M = D->M, Mp = D->Mp;
   const size_t es = D->es;
   hipStream_t s = D->ctx->stream;
-  char *cov = nullptr, *Lp = nullptr;
-  auto cleanup = [&]() {
-    (void)hipStreamSynchronize(s);
-    if (cov) (void)hipFree(cov);
-    if (Lp) (void)hipFree(Lp);
-  };
-  if (hipMalloc((void**)&cov, (size_t)Mp * Mp * es) != hipSuccess || hipMalloc((void**)&Lp, (size_t)Mp * Mp * es) != hipSuccess ||
-      hipMemsetAsync(Lp, 0, (size_t)Mp * Mp * es, s) != hipSuccess) {
+  DevTmp t_cov(s), t_lp(s);
+  if (hipMalloc((void**)&t_cov.p, (size_t)Mp * Mp * es) != hipSuccess || hipMalloc((void**)&t_lp.p, (size_t)Mp * Mp * es) != hipSuccess ||
+      hipMemsetAsync(t_lp.p, 0, (size_t)Mp * Mp * es, s) != hipSuccess) {
     snprintf(D->err, sizeof(D->err), "posterior_draws: out of device memory for two %lld x %lld matrices", (long long)Mp, (long long)Mp);
-    cleanup();
     return G3_ERR_NOMEM;
   }
+  char *cov = t_cov.p, *Lp = t_lp.p;
   int rc = posterior_cov(D, prog_f, Xs_dev, ldxs, cov, Mp);
   int tries = 0, fb = 0;
   double jit = 0;
@@ -1808,7 +1413,6 @@ extern "C" int g3_dist_posterior_draws(g3_dist* D, const g3_kernel_prog* prog_f,
   }
   if (tries_host) *tries_host = tries;
   if (fallback_host) *fallback_host = fb;
-  cleanup();
   return rc;
 }
 
@@ -1872,16 +1476,14 @@ extern "C" int g3_dist_gp_dlogp(g3_dist* D, const g3_kernel_prog* prog, const g3
   std::vector<int32_t> perm;
   const int call = perm_upto(D, nblk - 1, &perm);
   const int64_t apr = (int64_t)call * nb;               // alpha entries per rank in the padded gather
-  char* asend = D->send[0];                             // cmax >= cmax_all blocks of nb x nb: room for cmax_all * nb values
+  char* asend = D->asend;
   G3D_HIP(hipMemsetAsync(asend, 0, (size_t)apr * es, sA));
   if (D->rows_inv > 0) {
-    const unsigned grid = (unsigned)((D->rows_inv + 3) / 4);
-    if (D->dt == G3_F64)
-      hipLaunchKernelGGL(rows_dot_kernel<double>, dim3(grid), dim3(256), 0, sA, (const double*)Xinv, D->rows_inv, Np, Np,
-                         (const double*)D->avec, (double*)asend);
-    else
-      hipLaunchKernelGGL(rows_dot_kernel<float>, dim3(grid), dim3(256), 0, sA, (const float*)Xinv, D->rows_inv, Np, Np,
-                         (const float*)D->avec, (float*)asend);
+    by_dtype(D, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(rows_dot_kernel<T>, dim3((unsigned)((D->rows_inv + 3) / 4)), dim3(256), 0, sA, (const T*)Xinv, D->rows_inv, Np, Np,
+                         (const T*)D->avec, (T*)asend);
+    });
     G3D_HIP(hipGetLastError());
   }
   int rc = do_allgather(D, asend, D->agath, (size_t)apr * es, sA);
@@ -1892,15 +1494,14 @@ extern "C" int g3_dist_gp_dlogp(g3_dist* D, const g3_kernel_prog* prog, const g3
   for (int I = 0; I < nblk; ++I)
     for (int64_t r = 0; r < nb; ++r) {
       const size_t src = (size_t)perm[I] * nb + r, dst = (size_t)I * nb + r;
+      double v = host_at(D, hg.data(), src) * alpha_scale;
       if (D->dt == G3_F64) {
-        const double v = ((const double*)hg.data())[src] * alpha_scale;
         ((double*)ha.data())[dst] = v;
-        if (alpha_host && (int64_t)dst < D->N) alpha_host[dst] = v;
       } else {
-        const float v = (float)(((const float*)hg.data())[src] * alpha_scale);
-        ((float*)ha.data())[dst] = v;
-        if (alpha_host && (int64_t)dst < D->N) alpha_host[dst] = (double)v;
+        ((float*)ha.data())[dst] = (float)v;
+        v = (double)(float)v;                  // the caller gets what the device will read
       }
+      if (alpha_host && (int64_t)dst < D->N) alpha_host[dst] = v;
     }
   G3D_HIP(hipMemcpyAsync(D->alpha_dev, ha.data(), ha.size(), hipMemcpyHostToDevice, sA));
   // ---- my rows of K^-1 = X X^T, lower part
@@ -1931,8 +1532,7 @@ extern "C" int g3_dist_gp_dlogp(g3_dist* D, const g3_kernel_prog* prog, const g3
   const int ns = map->nslots;
   std::vector<double> acc(ns > 0 ? ns : 1, 0.0), part(ns > 0 ? ns : 1, 0.0);
   for (int I : D->my_blocks) {
-    const int64_t r0 = (int64_t)I * nb;
-    const int64_t nv = D->N - r0 < nb ? D->N - r0 : nb;
+    const int64_t r0 = (int64_t)I * nb, nv = valid_rows(D, I);
     if (nv <= 0 || ns == 0) continue;
     G3D_RC(D->ctx, g3i_gram_grad(D->ctx, prog, map, X_dev, D->N, ldx, D->d, D->dt, D->Kinv + (size_t)D->loff[I] * Np * es, Np,
                                  D->alpha_dev, part.data(), r0, nv));
@@ -1954,7 +1554,7 @@ extern "C" int g3_dist_comm_stats(g3_dist* D, double out_host[9]) {
   if (!out_host) return -2;
   g3_dev_guard _dg(D->ctx);
   G3D_HIP(hipStreamSynchronize(D->ctx->stream));
-  if (D->s_chain) G3D_HIP(hipStreamSynchronize(D->s_chain));
+  G3D_HIP(hipStreamSynchronize(D->s_chain));
   G3D_HIP(hipStreamSynchronize(D->s_look));
   G3D_HIP(hipStreamSynchronize(D->s_bulk));
   double ms[G3_NKIND] = {0, 0, 0, 0, 0};

@@ -335,16 +335,9 @@ static inline void trsm_ops_rec(TrsmOps* ops, int64_t c0, int64_t n) {
 // a full one.  Round-robin would leave the last rank at 1.4x.  Deterministic (ties: lowest rank): every rank computes
 // the same table, and g3py_amd/distributed.py::deal_blocks mirrors it line by line.
 #include <algorithm>
-static inline void g3h_deal(int P, int nblk, std::vector<int>* owner, int snake = 0) {
+static inline void g3h_deal(int P, int nblk, std::vector<int>* owner) {
   owner->assign(nblk > 0 ? nblk : 0, 0);
   if (P < 1) return;
-  if (snake) {            // G3_DIST_DEAL=snake: the boustrophedon of rounds 1-4 (A/B measurements)
-    for (int I = 0; I < nblk; ++I) {
-      const int r = I % (2 * P);
-      (*owner)[I] = r < P ? r : 2 * P - 1 - r;
-    }
-    return;
-  }
   std::vector<int64_t> load(P, 0);
   std::vector<int> order(P);
   for (int top = nblk - 1; top >= 0; top -= P) {
@@ -426,6 +419,41 @@ static inline void g3h_stair_chunks(const std::vector<int64_t>& seg_rows, const 
   }
 }
 
+// The three staircase launches of step k of that sweep (g3_dist.hip::factor).  Of a rank's row blocks I (my_blocks ascending,
+// block I at local row loff[I], rows_mat rows in all) and the rr right-hand-side rows behind them, panel k updates
+//   a   block column k+1 of the blocks I >= k+2 and of the right-hand-side rows     d1  block column k+2 of the same rows
+//   d2  block columns k+3 .. I of the blocks I >= k+3, and k+3 .. nblk-1 of the right-hand-side rows
+// lo: first local row (the segments follow one another); diag: the segment ends in its block's diagonal block; the launch
+// starts at block column k+1+blk0 and multiplies with entries [blk0, blk0 + nblk) of the panel's gather table.
+enum G3hStep { G3H_STEP_A = 0, G3H_STEP_D1 = 1, G3H_STEP_D2 = 2 };
+struct G3hStepSegments {
+  int64_t lo;
+  std::vector<int64_t> rows, cols, diag;
+  int blk0, nblk;
+};
+static inline G3hStepSegments g3h_step_segments(const std::vector<int>& my_blocks, const std::vector<int64_t>& loff, int64_t nb, int nblk,
+                                                int64_t rows_mat, int64_t rr, int k, G3hStep which) {
+  G3hStepSegments s;
+  s.lo = -1;
+  s.blk0 = (int)which;
+  s.nblk = which == G3H_STEP_D2 ? nblk - k - 3 : (k + 1 + (int)which < nblk ? 1 : 0);
+  if (s.nblk < 1) return s;
+  const int first = which == G3H_STEP_D2 ? k + 3 : k + 2;
+  auto push = [&](int64_t row, int64_t rows, int64_t cols, bool diag) {
+    if (s.lo < 0) s.lo = row;
+    s.rows.push_back(rows);
+    s.cols.push_back(cols);
+    s.diag.push_back(diag);
+  };
+  for (int I : my_blocks)
+    if (I >= first) {
+      const int ncol = which == G3H_STEP_D2 ? I - k - 2 : 1;
+      push(loff[I], nb, (int64_t)ncol * nb, k + 1 + s.blk0 + ncol - 1 == I);
+    }
+  if (rr > 0) push(rows_mat, rr, (int64_t)s.nblk * nb, false);
+  return s;
+}
+
 
 // ---- CholeskyRobust's jitter schedule (g3py/libs/tensors.py:203-213): dK = mean(diag) * 1e-6 (float32 constants, as
 // the reference's Theano graph has them), non-positive diagonals lifted by mean * 1e-6 - min, then up to 20 retries
@@ -465,6 +493,16 @@ static inline int g3h_ring_take(bool* busy, int nslots, int* next, int* last, bo
   busy[s] = false;
   *last = s;
   return s;
+}
+// A stream the ring has worked on is drained and about to be destroyed.  Every slot whose event has completed (done(i)) is
+// free -- all events recorded on that stream have, whichever stream the ring moved on to since -- so that no event of a
+// stream that is gone is ever waited for; if the ring's current stream is the one going away (`current`), the last slot has
+// no stream left to record its event on either.
+template <typename Done>
+static inline void g3h_ring_forget(bool* busy, int nslots, int* last, bool current, Done done) {
+  for (int i = 0; i < nslots; ++i)
+    if (busy[i] && done(i)) busy[i] = false;
+  if (current) *last = -1;
 }
 
 // ---- Gram fast paths: recognise  var * k(x[:, 0:d]) [+ pvar * COS(x[:, 0:d])] [+ Noise]  (compile-time kernels of

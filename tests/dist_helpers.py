@@ -288,7 +288,8 @@ def native_worker(rank, world, port, N, d, M, nb, transport, spec_f, noise, out_
             np.savez(out_path, logp=lp, mean=dgp.last['mean'], var=np.maximum(prior - dgp.last['ss'], 0),
                      tries=dgp.last['tries'], fallback=dgp.last['fallback'],
                      draws=dgp.last['draws'] if draws else np.zeros(0), slots=slots, alpha=alpha, logp_grad=lp3,
-                     comm_calls=sum(v['calls'] for v in cs.values()), comm_bytes=sum(v['bytes'] for v in cs.values()))
+                     comm_calls=sum(v['calls'] for v in cs.values()), comm_bytes=sum(v['bytes'] for v in cs.values()),
+                     bcast_calls=cs['bcast']['calls'], bcast_bytes=cs['bcast']['bytes'])     # of the two plain steps
         dgp.close()
     finally:
         dist.destroy_process_group()

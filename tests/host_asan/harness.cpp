@@ -2,7 +2,7 @@
 // shim"): g3py_amd/csrc/g3_host.h is pure C++ and is compiled here with g++ -fsanitize=address,undefined.  Every
 // table / schedule builder is driven over the shapes the library produces (and some it never should) and its output
 // is checked the way the device consumes it: the tile lookup of the GEMM kernel, the op list of the stripe solve, the
-// chunking of the multi-GPU staircase, the recursion's split point, the panel-width ladder, panel boundaries, the fast-path matcher, the program ring, the jitter schedule, the layout
+// chunking of the multi-GPU staircase and the segment lists of its steps, the recursion's split point, the panel-width ladder, panel boundaries, the fast-path matcher, the program ring, the jitter schedule, the layout
 // of the batched entry points' device buffer and the host expansion of a chain member.
 // TEST INFRASTRUCTURE: never linked into the product.
 #include <math.h>
@@ -336,6 +336,38 @@ static void test_ring_and_jitter() {
     CHECK(wait == (it >= 8));          // a slot is only waited for once the ring has wrapped onto it
     CHECK(last == s && !busy[s]);
   }
+  // A model of the ring across streams (g3i_upload_prog + g3i_ctx_forget_stream): a slot's event is recorded on the stream the
+  // slot was consumed on, when the NEXT slot is taken.  The context alternates between its own stream (0) and the chain
+  // streams of drivers that come and go (1, 2, ...: the entry points of the multi-GPU driver switch to them); when a driver is
+  // destroyed its drained stream is forgotten.  No take may ever wait for an event of a stream that is gone -- also when the
+  // ring had moved back to stream 0 before the destruction, the case a rule that only looks at the current stream misses
+  for (int back_first : {0, 1})
+    for (int uploads_between : {0, 1, 3}) {
+      const int NS = 8;
+      bool rb[NS] = {false};
+      int rnext = 0, rlast = -1, ev_stream[NS], cur_stream = 0, prog_stream = -1, alive = 0;
+      for (int i = 0; i < NS; ++i) ev_stream[i] = -1;
+      auto take = [&]() {
+        bool wait; int mark;
+        const int s = g3h_ring_take(rb, NS, &rnext, &rlast, &wait, &mark);
+        if (mark >= 0) { CHECK(prog_stream == 0 || prog_stream == alive); ev_stream[mark] = prog_stream; }
+        if (wait) CHECK(ev_stream[s] == 0 || ev_stream[s] == alive);      // never an event of a destroyed stream
+        prog_stream = cur_stream;
+      };
+      for (int driver = 1; driver <= 6; ++driver) {
+        alive = driver;
+        cur_stream = driver;                       // an entry point: a few programs on the driver's chain stream
+        for (int i = 0; i < 3; ++i) take();
+        cur_stream = 0;
+        if (back_first) for (int i = 0; i < uploads_between; ++i) take();      // ... the caller's own work before the destruction
+        // destruction: the chain stream is drained (its events are done), the caller's stream may still be busy
+        g3h_ring_forget(rb, NS, &rlast, prog_stream == driver, [&](int i) { return ev_stream[i] == driver; });
+        if (prog_stream == driver) prog_stream = -1;
+        alive = 0;
+        for (int i = 0; i < NS; ++i) CHECK(!(rb[i] && ev_stream[i] == driver));
+        if (!back_first) for (int i = 0; i < uploads_between; ++i) take();
+      }
+    }
   // the reference's schedule: dK = mean * 1e-6 (float32 constant), x10 per retry, lift when min <= 0
   G3hJitter j(2.0, 0.5);
   CHECK(j.lift == 0.0 && fabs(j.value() - 2.0 * (double)1e-6f) < 1e-18 && j.usable());
@@ -386,6 +418,57 @@ static void test_dealing() {
           }
         }
     }
+}
+
+// the three staircase launches of a step of the multi-GPU sweep (g3h_step_segments), brute force: over every rank and
+// step the cells (row block, column block) of a, d1 and d2 are exactly {I owned, I >= k+2, k+1 <= J <= I} plus the
+// right-hand-side rows x {k+1 <= J < nblk}, each once; a segment is flagged where its last block is the diagonal one
+static void test_step_segments() {
+  const int64_t nb = 256;
+  const int RHS = -1;       // the row "block" of the right-hand-side rows
+  for (int P : {1, 2, 3, 5, 8})
+    for (int nblk : {1, 2, 3, 7, 32, 33})
+      for (int64_t rr : {(int64_t)0, (int64_t)128, (int64_t)384}) {
+        std::vector<int> owner;
+        g3h_deal(P, nblk, &owner);
+        for (int rank = 0; rank < P; ++rank) {
+          std::vector<int> mine;
+          std::vector<int64_t> loff(nblk, -1);
+          for (int I = 0; I < nblk; ++I)
+            if (owner[I] == rank) { loff[I] = (int64_t)mine.size() * nb; mine.push_back(I); }
+          const int64_t rows_mat = (int64_t)mine.size() * nb;
+          for (int k = 0; k + 1 < nblk; ++k) {
+            std::map<std::pair<int, int>, int> cover;
+            for (G3hStep which : {G3H_STEP_A, G3H_STEP_D1, G3H_STEP_D2}) {
+              const G3hStepSegments s = g3h_step_segments(mine, loff, nb, nblk, rows_mat, rr, k, which);
+              CHECK(s.rows.size() == s.cols.size() && s.rows.size() == s.diag.size());
+              if (s.rows.empty()) continue;
+              CHECK(s.blk0 == (int)which && s.nblk >= 1 && k + 1 + s.blk0 + s.nblk <= nblk);   // inside the gather table of panel k
+              int64_t row = s.lo;
+              for (size_t i = 0; i < s.rows.size(); ++i) {
+                int I = RHS;
+                if (row < rows_mat) {          // a row block of the matrix: whole, and where the plan put it
+                  CHECK(row % nb == 0 && s.rows[i] == nb);
+                  I = mine[(size_t)(row / nb)];
+                  CHECK(loff[I] == row);
+                } else {
+                  CHECK(row == rows_mat && s.rows[i] == rr && rr > 0 && i + 1 == s.rows.size());
+                }
+                CHECK(s.cols[i] > 0 && s.cols[i] % nb == 0 && s.cols[i] <= (int64_t)s.nblk * nb);
+                const int J0 = k + 1 + s.blk0, J1 = J0 + (int)(s.cols[i] / nb) - 1;
+                for (int J = J0; J <= J1; ++J) cover[{I, J}]++;
+                CHECK((s.diag[i] != 0) == (J1 == I));
+                row += s.rows[i];
+              }
+            }
+            size_t want = 0;
+            for (int I : mine)
+              for (int J = k + 1; I >= k + 2 && J <= I; ++J) { CHECK((cover[{I, J}] == 1)); ++want; }
+            for (int J = k + 1; rr > 0 && J < nblk; ++J) { CHECK((cover[{RHS, J}] == 1)); ++want; }
+            CHECK(cover.size() == want);
+          }
+        }
+      }
 }
 
 // the batched entry points' device buffer (g3h_member_layout) and the host expansion of a chain member (MemberProgs)
@@ -461,6 +544,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   test_dealing();
+  test_step_segments();
   test_rasters();
   test_trsm_ops();
   test_split_and_ladder();

@@ -143,6 +143,35 @@ def test_native_driver_matches_oracle(tmp_path, world, N, nb, M):
     _check_gradient(r, orc.with_noise(spec_f, 0.1), X, y, d)
 
 
+@pytest.mark.parametrize('world,N,nb,M,fullinv', [(2, 1169, 384, 130, None), (3, 1169, 384, 130, None), (2, 1500, 256, 50, '0')])
+def test_native_driver_stripe_solve(tmp_path, monkeypatch, world, N, nb, M, fullinv):
+    """the panel solve WITHOUT the full inverse (solve_and_gather's g3_trsm_rlt branch, the head rows released first): a
+    block height that is not 128 * 2^q (384: four blocks, the last one ragged) keeps the stripe solve by plan, and
+    G3_DIST_FULLINV=0 forces it at nb = 256.  Same assertions and tolerances as test_native_driver_matches_oracle"""
+    import torch.multiprocessing as mp
+    from oracle import g3_oracle as orc
+    if fullinv is not None:
+        monkeypatch.setenv('G3_DIST_FULLINV', fullinv)
+    d = 4
+    spec_f = ('SE', 1.0, np.ones(d), None)
+    out = str(tmp_path / 'res.npz')
+    mp.spawn(native_worker, args=(world, _free_port(), N, d, M, nb, 'callbacks', spec_f, 0.1, out, False, 0, 'f64', True),
+             nprocs=world, join=True)
+    r = np.load(out)
+    # the plan did take the stripe solve: a diagonal block then travels as L (nb x nb) WITH its nb x 128 block inverses (the
+    # product path broadcasts the nb x nb inverse alone); two evaluations, each nblk of them and one broadcast of a (1 x Np)
+    nblk = -(-N // nb)
+    assert int(r['bcast_calls']) == 2 * (nblk + 1)
+    assert int(r['bcast_bytes']) == 2 * 8 * (nblk * (nb * nb + nb * 128) + nblk * nb)
+    X, y, Xs = synth(N, d, M, 77)
+    gp = orc.GP(spec_f, 0.1)
+    ref = gp.logp(X, y)
+    assert abs(float(r['logp']) - ref) <= 1e-10 * abs(ref)
+    np.testing.assert_allclose(r['mean'], gp.mean(Xs, X, y), atol=1e-8)
+    np.testing.assert_allclose(r['var'], gp.variance(Xs, X, y), atol=1e-8)
+    _check_gradient(r, orc.with_noise(spec_f, 0.1), X, y, d)
+
+
 def test_native_driver_one_rank_through_rccl(tmp_path):
     """the product transport: the library dlopens librccl, creates its two communicators from ids made by rank 0 and
     issues ncclBroadcast / ncclAllGather / ncclAllReduce on its own streams (world 1: all a one-GPU box allows)"""
