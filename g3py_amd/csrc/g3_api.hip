@@ -5,7 +5,7 @@
 #include <stdlib.h>
 
 // ----------------------------------------------------------------------------- context
-extern "C" int g3_version(void) { return 101; }
+extern "C" int g3_version(void) { return 102; }
 
 static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out);
 extern "C" int g3_ctx_create(int device, g3_ctx** out) { return ctx_create_impl(device, nullptr, out); }
@@ -498,16 +498,27 @@ logp_finish_kernel(const T* L, int64_t n, int64_t npad, int64_t ld, const T* __r
 template <typename T>
 __global__ void __launch_bounds__(256)
 rows_dot_ss_kernel(const T* __restrict__ V, int64_t n, int64_t ld, const T* __restrict__ a,
-                   T* __restrict__ dot, T* __restrict__ ss, int64_t vstride, int64_t astride, int64_t ostride) {
+                   T* __restrict__ dot, T* __restrict__ ss, int64_t vstride, int64_t astride, int64_t ostride, int64_t tri) {
   __shared__ double sd[4], sq[4];
   // grid.y = batch member: V, a and the outputs vstride / astride / ostride elements apart (0, 0, 0 for one problem)
   V += (int64_t)blockIdx.y * vstride;
   if (a) a += (int64_t)blockIdx.y * astride;
   if (dot) dot += (int64_t)blockIdx.y * ostride;
   if (ss) ss += (int64_t)blockIdx.y * ostride;
-  const T* v = V + (int64_t)blockIdx.x * ld;
+  // tri > 0: V is upper triangular and square, row i is read from column i on (nothing left of the diagonal is touched) and
+  // the rows [n, tri) of the padding get zeros.  tri == 0: the whole row.  Either way thread t takes every 256th column from
+  // the start of what is read, so the summation order of a row is fixed
+  const int64_t i = blockIdx.x;
+  if (tri > 0 && i >= n) {
+    if (threadIdx.x == 0) {
+      if (dot) dot[i] = T(0);
+      if (ss) ss[i] = T(0);
+    }
+    return;
+  }
+  const T* v = V + i * ld;
   double d = 0, q = 0;
-  for (int64_t j = threadIdx.x; j < n; j += 256) {
+  for (int64_t j = (tri > 0 ? i : 0) + threadIdx.x; j < n; j += 256) {
     const double x = (double)v[j];
     if (a) d += x * (double)a[j];
     q += x * x;
@@ -681,9 +692,9 @@ rows_dot_ss_member_kernel(const T* __restrict__ V, int64_t m, int64_t n, int64_t
 
 static int rows_dot_ss_launch(g3_ctx* ctx, const void* V, int64_t m, int64_t n, int64_t ld, const void* a,
                               g3_dtype dt, void* dot, void* ss, int batch = 1, int64_t vstride = 0, int64_t astride = 0,
-                              int64_t ostride = 0) {
+                              int64_t ostride = 0, int64_t tri = 0) {
   if (m == 0) return G3_OK;
-  if (batch > 1 && m <= 1024) {
+  if (batch > 1 && m <= 1024 && tri == 0) {
     if (dt == G3_F64)
       hipLaunchKernelGGL((rows_dot_ss_member_kernel<double>), dim3((unsigned)batch), dim3(256), 0, ctx->stream,
                          (const double*)V, m, n, ld, (const double*)a, (double*)dot, (double*)ss, vstride, astride, ostride);
@@ -695,10 +706,10 @@ static int rows_dot_ss_launch(g3_ctx* ctx, const void* V, int64_t m, int64_t n, 
   }
   if (dt == G3_F64)
     hipLaunchKernelGGL((rows_dot_ss_kernel<double>), dim3((unsigned)m, (unsigned)batch), dim3(256), 0, ctx->stream,
-                       (const double*)V, n, ld, (const double*)a, (double*)dot, (double*)ss, vstride, astride, ostride);
+                       (const double*)V, n, ld, (const double*)a, (double*)dot, (double*)ss, vstride, astride, ostride, tri);
   else
     hipLaunchKernelGGL((rows_dot_ss_kernel<float>), dim3((unsigned)m, (unsigned)batch), dim3(256), 0, ctx->stream,
-                       (const float*)V, n, ld, (const float*)a, (float*)dot, (float*)ss, vstride, astride, ostride);
+                       (const float*)V, n, ld, (const float*)a, (float*)dot, (float*)ss, vstride, astride, ostride, tri);
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -706,6 +717,12 @@ static int rows_dot_ss_launch(g3_ctx* ctx, const void* V, int64_t m, int64_t n, 
 int g3i_rows_dot_ss_batched(g3_ctx* ctx, const void* V, int64_t m, int64_t n, int64_t ld, const void* a, g3_dtype dt, void* dot,
                             void* ss, int batch, int64_t vstride, int64_t astride, int64_t ostride) {
   return rows_dot_ss_launch(ctx, V, m, n, ld, a, dt, dot, ss, batch, vstride, astride, ostride);
+}
+
+// the upper-triangular, square case (Y = L^-T of g3_gp_loo): rows [0, n) from their diagonal on, rows [n, npad) written as 0
+int g3i_rows_dot_ss_tri(g3_ctx* ctx, const void* Y, int64_t n, int64_t npad, int64_t ld, const void* a, g3_dtype dt, void* dot,
+                        void* ss) {
+  return rows_dot_ss_launch(ctx, Y, npad, n, ld, a, dt, dot, ss, 1, 0, 0, 0, npad);
 }
 
 extern "C" int g3_rows_dot_ss(g3_ctx* ctx, const void* V, int64_t m, int64_t n, int64_t ld,

@@ -27,7 +27,8 @@
 // Y (n x n, upper triangular on return) = L^-T and C (lower triangle) = K^-1 = Y Y^T.
 // Right-looking over NB-wide panels of columns: panel k of Y is final after the solve against
 // L_kk; it then updates the columns to its right (rows 0..r1 only: Y is upper triangular, so
-// no flop is spent on structural zeros) and adds its outer product to C.
+// no flop is spent on structural zeros) and adds its outer product to C.  C == nullptr: the Y half
+// alone (n^3 / 3 flops) -- the sweep without its SYRKs, for callers that want L^-T and not K^-1 (g3_gp_loo).
 // rows x row_bytes zeros at `pitch` for every batch member (grid.z), members `bstride` bytes apart
 __global__ void __launch_bounds__(256) zero2d_batched_kernel(char* __restrict__ p, size_t pitch, size_t row_bytes, int64_t rows, size_t bstride) {
   const size_t c = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
@@ -56,7 +57,7 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
   }
   hipStream_t sA = ctx->stream, sB = two ? ctx->side_stream : sA;
 
-  if (g3_nbatch(ctx) > 1 && ((n * es) % 16 == 0) && ((ldy * es) % 16 == 0) && ((ldc * es) % 16 == 0) &&
+  if (C && g3_nbatch(ctx) > 1 && ((n * es) % 16 == 0) && ((ldy * es) % 16 == 0) && ((ldc * es) % 16 == 0) &&
       ((((uintptr_t)Y | (uintptr_t)C) & 15) == 0) && ((g3_bstride_of(ctx, Y) * es) % 16 == 0) && ((g3_bstride_of(ctx, C) * es) % 16 == 0)) {
     // batch mode: every member's Y and K^-1 in two launches (one memset per member is 8192 stream operations for a chain
     // of 4096 members -- 15 ms of device time and 80 ms of host time for 2.5 ms of kernels)
@@ -69,7 +70,7 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
   } else {
     for (int b = 0; b < g3_nbatch(ctx); ++b) {
       G3_HIP(hipMemset2DAsync((char*)Y + (size_t)b * g3_bstride_of(ctx, Y) * es, (size_t)ldy * es, 0, (size_t)n * es, (size_t)n, sA));
-      G3_HIP(hipMemset2DAsync((char*)C + (size_t)b * g3_bstride_of(ctx, C) * es, (size_t)ldc * es, 0, (size_t)n * es, (size_t)n, sA));
+      if (C) G3_HIP(hipMemset2DAsync((char*)C + (size_t)b * g3_bstride_of(ctx, C) * es, (size_t)ldc * es, 0, (size_t)n * es, (size_t)n, sA));
     }
   }
   rc = g3i_diag_add(ctx, Y, n, ldy, dt, 1.0);
@@ -89,6 +90,7 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
                        -1.0, 1.0, dt, 0);
   };
   auto syrk = [&](int k) -> int {
+    if (!C) return G3_OK;
     return g3i_gemm_nt(ctx, C, ldc, Yp(r(k)), ldy, Yp(r(k)), ldy, r(k + 1), r(k + 1), r(k + 1) - r(k), 1.0, 1.0,
                        dt, 1);
   };

@@ -289,6 +289,9 @@ int g3i_gram_grad_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, c
                           int64_t astride, double* out_host, int64_t row0 = 0, int64_t nrows = -1);
 int g3i_rows_dot_ss_batched(g3_ctx* ctx, const void* V, int64_t m, int64_t n, int64_t ld, const void* a, g3_dtype dt, void* dot,
                             void* ss, int batch, int64_t vstride, int64_t astride, int64_t ostride);
+// rows_dot_ss over the upper triangle of a square Y (npad x npad): rows [0, n) from their diagonal on, rows [n, npad) get 0
+int g3i_rows_dot_ss_tri(g3_ctx* ctx, const void* Y, int64_t n, int64_t npad, int64_t ld, const void* a, g3_dtype dt, void* dot,
+                        void* ss);
 int g3i_ensure_invd(g3_ctx* ctx, int64_t n, g3_dtype dt);
 int g3i_ensure_work(g3_ctx* ctx, size_t bytes);
 int g3i_upload_prog(g3_ctx* ctx, const g3_kernel_prog* prog, int slot, const g3_kernel_prog** dptr);
@@ -319,6 +322,7 @@ int g3i_validate_prog(const g3_kernel_prog* p, int d);
 int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_prog* prog_dev, int batch, const void* X1, int64_t n1,
                  int64_t ldx1, const void* X2, int64_t n2, int64_t ldx2, int d, g3_dtype dt, void* K, int64_t ldk, int64_t n1pad,
                  int64_t n2pad, unsigned flags, int sym, int64_t kstride, int64_t diag_off, dim3 grid);
+// C == nullptr: Y = L^-T alone, the K^-1 product is not run
 int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* invd, g3_dtype dt, void* Y,
               int64_t ldy, void* C, int64_t ldc);
 

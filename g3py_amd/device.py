@@ -492,6 +492,21 @@ class Device:
         _check(self, rc, 'g3_gp_dlogp')
         return np.array(out[:gmap.nslots])
 
+    # ---- leave-one-out predictions from the factor
+    def gp_loo(self, N, L, W, a, Y, alpha, kdiag):
+        """after gp_factor: Y <- L^-T, alpha = K^-1 delta and kdiag = diag K^-1 (roundup(N) entries each, 0 from N on);
+        stream-ordered, the caller downloads"""
+        rc = self.lib.g3_gp_loo(self.ctx, L.ptr, N, L.ld, W.ptr, a.ptr, _lib.dtype_code(L.dtype), Y.ptr, Y.ld, alpha.ptr,
+                                kdiag.ptr)
+        _check(self, rc, 'g3_gp_loo')
+
+    def gp_loo_batched(self, B, N, K, kstride, W, a, Y, alpha, kdiag):
+        """after gp_factor_batched(_fields) on the same buffers: alpha and kdiag of every member, (B, roundup(N)) device
+        matrices; Y (one roundup(N)-square workspace) is needed above N = 256 only and may be None below"""
+        rc = self.lib.g3_gp_loo_batched(self.ctx, int(B), K.ptr, N, K.ld, int(kstride), W.ptr, a.ptr, _lib.dtype_code(K.dtype),
+                                        self._ptr(Y), alpha.ptr, kdiag.ptr)
+        _check(self, rc, 'g3_gp_loo_batched')
+
 
 atexit.register(Device.close_all)
 

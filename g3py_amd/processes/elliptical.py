@@ -174,7 +174,7 @@ class EllipticalProcess(StochasticProcess):
             self._workspace = ws
         Xd, Kd, ad, Wd = ws['Xd'], ws['Kd'], ws['ad'], ws['Wd']
         c = dict(key=key, X=X.copy(), y=y.copy(), N=N, d=d, Np=Np, Xd=Xd, Kd=Kd, Wd=Wd, ad=ad, mu=mu, det_m=det_m,
-                 delta=delta, delta_post=mapped_num - mu, stats=None, which=None)
+                 delta=delta, delta_post=mapped_num - mu, z=mapped_num, stats=None, which=None)
         c['same_delta'] = bool(np.array_equal(c['delta'], c['delta_post']))
         self._cache = c
         return c
@@ -193,7 +193,7 @@ class EllipticalProcess(StochasticProcess):
                 sp = None
             st, cross = self._dist_step(c, values, dl, sp)
             st['delta_finite'] = bool(finite)
-            c['stats'], c['which'], c['grad'], c['cross'] = st, which, None, cross
+            c['stats'], c['which'], c['grad'], c['cross'], c['loo'] = st, which, None, cross, None
             return st
         dvec = self._workspace['dvec']
         dev.copy_in(dvec, np.where(np.isfinite(dl), dl, 0).astype(self.dtype))
@@ -203,6 +203,7 @@ class EllipticalProcess(StochasticProcess):
         c['stats'], c['which'] = st, which
         c['grad'] = None            # K^-1 / alpha pieces of th_dlogp belong to this factorisation
         c['cross'] = None           # so does the last cross solve
+        c['loo'] = None             # and the leave-one-out vectors
         return st
 
     def _cross(self, c, values, space, noise, kernel=None):

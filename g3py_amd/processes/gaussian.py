@@ -9,7 +9,8 @@ from .elliptical import EllipticalProcess, SENTINEL
 
 def logp_cho_diag(value, mu, sd, mapping, values, dtype):
     """WarpedGaussianDistribution.logp_cho with a DIAGONAL factor (gaussian.py:42-54,192-241):
-    independent marginals, O(M) host arithmetic on device-produced vectors."""
+    independent marginals, O(M) host arithmetic on device-produced vectors.  (loo_assemble below holds the same density
+    and the same -1e30 conditions for B rows of hyper values at once: change the two together.)"""
     t = np.dtype(dtype).type
     value = np.asarray(value, dtype=dtype)
     with np.errstate(all='ignore'):
@@ -25,6 +26,66 @@ def logp_cho_diag(value, mu, sd, mapping, values, dtype):
     if np.any(~np.isfinite(lcho)):
         return t(SENTINEL)
     return r
+
+
+def gauss_hermite(f, mu, sigma, n, dtype):
+    """E f(N(mu, sigma^2)) by n-point Gauss-Hermite quadrature (gaussian.py:162-174)"""
+    t = np.dtype(dtype).type
+    _a, _w = np.polynomial.hermite.hermgauss(n)
+    a = _a.astype(dtype)[:, None]
+    w = _w.astype(dtype)
+    grille = mu + sigma * t(np.sqrt(2)) * a
+    return np.dot(w, f(grille.flatten()).reshape(grille.shape)) / t(np.sqrt(np.pi))
+
+
+def loo_assemble(alpha, kdiag, z, mapping, values, y=None, dtype=np.float64, hermite=None, mean=True, std=True, var=False,
+                 median=False, logpred=True):
+    """The O(N) host side of leave-one-out: from alpha = K^-1 (z - m(X)) and kdiag = diag K^-1 of the factored, noisy K,
+    observation i predicted from all the others is latent-normal with
+        loc_i = z_i - alpha_i / kdiag_i        sd_i = 1 / sqrt(kdiag_i)
+    (z = T^-1(y), scrubbed by the caller where it must be).  Returns a DictObj under predict's keys -- mean, variance, std,
+    median through the mapping (hermite=None: a plain process, mapping(loc) and sd^2 as elliptical.py:190-200; hermite=n:
+    the warped process's n-point Gauss-Hermite moments, gaussian.py:127-157) -- plus `logpredictive` =
+    logp_cho_diag(y, loc, sd, ...), the summed log density of every y_i under its own leave-one-out predictive.
+    Two-dimensional alpha / kdiag / z (rows of a chain, `values` from _values_rows): only `logpredictive`, one per row --
+    logp_cho_diag's density and sentinel conditions as array passes over the rows, with z = mapping.inv_rows(y) as the
+    caller has it (NOT scrubbed: a row with a non-finite entry takes the sentinel) and the mapping's logdet_dinv_rows;
+    the curve switches and `hermite` play no part there.  No device, no process: a pure function of its arguments."""
+    from ..libs import DictObj
+    t = np.dtype(dtype).type
+    alpha, kdiag, z = (np.asarray(v, dtype=dtype) for v in (alpha, kdiag, z))
+    with np.errstate(all='ignore'):
+        loc = z - alpha / kdiag
+        sd = t(1) / np.sqrt(kdiag)
+    out = DictObj()
+    if alpha.ndim == 2:
+        B, N = alpha.shape
+        yv = np.asarray(y, dtype=dtype)
+        with np.errstate(all='ignore'):           # logp_cho_diag, row by row of the chain
+            delta = z - loc
+            det_m = np.asarray(mapping.logdet_dinv_rows(yv, values, B), dtype=dtype)
+            lcho = delta / sd
+            r = (t(-0.5) * t(N) * np.log(t(2.0 * np.pi)) + t(-0.5) * (lcho * lcho).sum(axis=1) - np.log(sd).sum(axis=1) + det_m)
+        bad = ~(np.isfinite(delta).all(axis=1) & np.isfinite(det_m) & np.isfinite(sd).all(axis=1) & np.isfinite(lcho).all(axis=1))
+        out['logpredictive'] = np.where(bad, t(SENTINEL), r).astype(dtype)
+        return out
+    with np.errstate(all='ignore'):
+        if hermite is None:
+            m, v = (mapping(loc, values), sd * sd) if (mean or std or var) else (None, None)
+        else:
+            m = gauss_hermite(lambda u: mapping(u, values), loc, sd, hermite, dtype) if (mean or std or var) else None
+            v = gauss_hermite(lambda u: mapping(u, values) ** 2, loc, sd, hermite, dtype) - m ** 2 if (std or var) else None
+        if mean:
+            out['mean'] = m
+        if var:
+            out['variance'] = v
+        if std:
+            out['std'] = np.sqrt(v)
+        if median:
+            out['median'] = mapping(loc, values)
+    if logpred:
+        out['logpredictive'] = logp_cho_diag(y, loc, sd, mapping, values, dtype)
+    return out
 
 
 class _Ref:
@@ -107,9 +168,10 @@ class GaussianProcess(EllipticalProcess):
             prog = self._prog(self.f_kernel_noise, values, d)
             gmap = dev.grad_layout(prog)
             ws = self._workspace                 # K^-1 workspaces live with the factor workspace (same data set)
-            if 'Y' not in ws:
-                ws['Y'], ws['Kinv'] = dev.alloc(Np, Np, self.dtype), dev.alloc(Np, Np, self.dtype)
-                ws['alpha'] = dev.alloc(1, Np, self.dtype)
+            if 'Y' not in ws:                    # (loo shares Y: scratch in both)
+                ws['Y'] = dev.alloc(Np, Np, self.dtype)
+            if 'Kinv' not in ws:
+                ws['Kinv'], ws['alpha'] = dev.alloc(Np, Np, self.dtype), dev.alloc(1, Np, self.dtype)
             Y, Kinv, alpha = ws['Y'], ws['Kinv'], ws['alpha']
             ad = c['ad']
             if s != 1.0:      # G = s alpha alpha^T - K^-1: hand the device sqrt(s) a, it returns sqrt(s) alpha
@@ -557,6 +619,90 @@ class GaussianProcess(EllipticalProcess):
         loc, sd, values = self._loc_sd(space, inputs, outputs, params, prior, noise, sd_noise=True)
         return logp_cho_diag(vector, loc, sd, self.f_mapping, values, self.dtype)
 
+    # ---- leave-one-out cross-validation from the factor (no counterpart in the reference: its scores / Experiment
+    #      harness, models.py:449-469, refits per hold-out split)
+    _LOO_HERMITE = None          # mean / variance of a plain process: mapping(loc) and sd^2 (elliptical.py:190-200)
+
+    def _loo_guard(self, inputs=None):
+        if self._dist is not None:
+            raise _lib.G3Error('loo runs on one GPU')
+        if inputs is None and not self.is_observed:
+            raise _lib.G3Error('loo needs observations')
+
+    def loo(self, params=None, inputs=None, outputs=None, mean=True, std=True, var=False, median=False, logpred=True):
+        """Every observation predicted from all the others, from the Cholesky factor `logp` already paid for: a DictObj
+        under predict's keys (mean, variance, std, median: length N) plus `logpredictive`, the sum over i of
+        logpredictive(vector=[y_i], space=[x_i]) after observing everything but i.  With alpha = K^-1 delta and
+        c_i = [K^-1]_ii of the factored (possibly jittered) noisy covariance the latent predictive of y_i is
+        N(z_i - alpha_i / c_i, 1 / c_i); the device forms L^-T and both vectors (g3_gp_loo: N^3 / 3 flops, half of
+        dlogp's K^-1), the host the O(N) rest (loo_assemble).  A `logp` on the same parameters before it is not repeated.
+        Where th_loglike takes its constant branch, logpredictive is the -1e30 sentinel and the curves come from the
+        scrubbed observations, as predict's do."""
+        self._loo_guard(inputs)
+        params, _, inputs, outputs, _ = self._call_defaults(params, None, inputs, outputs, False, False)
+        dev = self.device
+        values, _ = self._values(params)
+        c = self._factor(values, inputs, outputs)
+        const = not (np.all(np.isfinite(c['delta'])) and np.all(np.isfinite(c['det_m'])))     # gaussian.py:234-235
+        st = self._solve(c, values, 'post' if const else 'logp')
+        if c.get('loo') is None:
+            N, Np, ws = c['N'], c['Np'], self._workspace
+            if 'Y' not in ws:                    # (dlogp's Y: scratch in both)
+                ws['Y'] = dev.alloc(Np, Np, self.dtype)
+            if 'loo' not in ws:
+                ws['loo'] = dev.alloc(2, Np, self.dtype)         # alpha, kdiag
+            vec = ws['loo']
+            dev.gp_loo(N, c['Kd'], c['Wd'], c['ad'], ws['Y'], vec, dev.wrap(vec.offset(1), 1, Np, Np, self.dtype, keep=vec))
+            c['loo'] = dev.download(vec, 2, N)
+        alpha, kdiag = c['loo']
+        out = loo_assemble(alpha, kdiag, c['z'], self.f_mapping, values, y=c['y'], dtype=self.dtype,
+                           hermite=self._LOO_HERMITE, mean=mean, std=std, var=var, median=median, logpred=logpred)
+        if logpred and (const or not np.isfinite(st['logdet']) or st['nonfinite'] > 0):           # gaussian.py:234-237
+            out['logpredictive'] = self.dtype.type(SENTINEL)
+        return out
+
+    def loo_chain(self, chain, batch=None):
+        """loo(...).logpredictive for every row of a flat-parameter chain, shape (rows,): a model-comparison score over a
+        whole trace.  The block structure is logp_chain's -- `batch` rows share ONE Gram launch and ONE factorisation
+        sweep -- followed by ONE g3_gp_loo_batched (N <= 256: one workgroup per member) and one download of the members'
+        alpha and kdiag; the rest is array arithmetic over the rows (loo_assemble), which is what the call spends most of
+        its time in at small N (profiles/loo.md).  Rows
+        that logp_chain sends to its -1e30 sentinel get the sentinel.  A predictive score, not a posterior density: no
+        prior and no Jacobian-of-transform terms."""
+        self._loo_guard()
+        chain = np.atleast_2d(np.asarray(chain, dtype=np.float64))
+        n_rows = len(chain)
+        t = self.dtype.type
+        out = np.empty(n_rows, dtype=self.dtype)
+        if n_rows == 0:
+            return out
+        dev = self.device
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+            n_rows, batch, lambda Np, kstride: int(4e9 // (kstride * self.dtype.itemsize)))
+        K, W, a = ws['K'], ws['W'], ws['a']
+        vec = dev.alloc(2 * batch, Np, self.dtype)               # a block's alpha rows, then its kdiag rows: one download
+        Y = dev.alloc(Np, Np, self.dtype) if Np > 2 * _lib.G3_PAD else None
+        try:
+            for lo in range(0, n_rows, batch):
+                hi = min(lo + batch, n_rows)
+                B = hi - lo
+                values_b, _ = self._values_rows(chain[lo:hi])
+                delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
+                st = self._chain_factor_block(self._chain_members(self.f_kernel_noise, values_b, d, B), delta, Xd, N, d, K,
+                                              kstride, W, a)
+                dev.gp_loo_batched(B, N, K, kstride, W, a, Y, vec, dev.wrap(vec.offset(B), B, Np, Np, self.dtype, keep=vec))
+                both = dev.download(dev.wrap(vec.ptr, 2 * B, Np, Np, self.dtype, keep=vec), 2 * B, N)
+                with np.errstate(all='ignore'):
+                    z = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
+                lp = loo_assemble(both[:B], both[B:], z, self.f_mapping, values_b, y=y, dtype=self.dtype)['logpredictive']
+                bad |= ~np.isfinite(st[:, 0]) | (st[:, 2] > 0)                                # gaussian.py:237
+                out[lo:hi] = np.where(bad, t(SENTINEL), lp)
+        finally:
+            for buf in (vec, Y, Xd):
+                if buf is not None:
+                    buf.free()
+        return out
+
     # ---- quantiles and draws (gaussian.py:56-97)
     def quantiler(self, params=None, space=None, inputs=None, outputs=None, q=0.975, prior=False, noise=False,
                   simulations=None):
@@ -603,6 +749,7 @@ class GaussianProcess(EllipticalProcess):
 
 class WarpedGaussianProcess(GaussianProcess):
     _CHAIN_PREDICT = False       # predict_chain takes the loop of single predictions
+    _LOO_HERMITE = 10            # loo's mean / variance: the Gauss-Hermite moments of th_mean / th_variance
 
     def __init__(self, *args, **kwargs):
         if 'name' not in kwargs:
@@ -611,12 +758,7 @@ class WarpedGaussianProcess(GaussianProcess):
 
     def gauss_hermite(self, f, mu, sigma, n=10):
         """gaussian.py:162-174"""
-        t = self.dtype.type
-        _a, _w = np.polynomial.hermite.hermgauss(n)
-        a = _a.astype(self.dtype)[:, None]
-        w = _w.astype(self.dtype)
-        grille = mu + sigma * t(np.sqrt(2)) * a
-        return np.dot(w, f(grille.flatten()).reshape(grille.shape)) / t(np.sqrt(np.pi))
+        return gauss_hermite(f, mu, sigma, n, self.dtype)
 
     def th_mean(self, space, inputs, outputs, vector, params, prior=False, noise=False, n=10):
         loc, sd, values = self._loc_sd(space, inputs, outputs, params, prior, noise)

@@ -453,10 +453,12 @@ class StochasticProcess:
                             samples=samples, prior=prior, noise=noise)['samples']
 
     def scores(self, params=None, space=None, hidden=None, inputs=None, outputs=None, logp=False, logpred=False,
-               bias=True, variance=False, median=False, *args, **kwargs):
+               bias=True, variance=False, median=False, *args, loo=False, **kwargs):
         """scoring harness over mean / variance / median / logpredictive against the hidden truth
         (boundary: models.py:449-469 -- the keys `_l1`, `_l2`, `_mse`, `_rmse`, `_median_l1`,
-        `_median_l2`, `_logp`, `_loglike`, `_logprior`, `_nlpd`)"""
+        `_median_l2`, `_logp`, `_loglike`, `_logprior`, `_nlpd`).  loo=True (keyword only; no counterpart in the reference) adds the
+        leave-one-out scores of the OBSERVATIONS from the factor logp already paid for (GaussianProcess.loo): `_loo_nlpd`
+        = -logpredictive / N, `_loo_l1` and `_loo_l2`, the mean absolute and squared error of the leave-one-out mean"""
         truth = self.hidden if hidden is None else hidden
         pred = self.predict(params=params, space=space, inputs=inputs, outputs=outputs, mean=True, var=variance,
                             median=median, distribution=logpred)
@@ -475,6 +477,14 @@ class StochasticProcess:
             out.update(_logp=self.logp(params), _loglike=self.loglike(params), _logprior=self.logp(params, prior=True))
         if logpred:
             out['_nlpd'] = -pred.logpredictive(truth) / len(truth)
+        if loo:
+            if not hasattr(self, 'loo'):
+                from .._lib import G3Error
+                raise G3Error('leave-one-out scores are not available for %s' % type(self).__name__)
+            held = self.loo(params=params, inputs=inputs, outputs=outputs, mean=True, std=False, logpred=True)
+            seen = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
+            out.update(_loo_nlpd=-held.logpredictive / len(seen), _loo_l1=np.mean(np.abs(held.mean - seen)),
+                       _loo_l2=np.mean((held.mean - seen) ** 2))
         return out
 
     def logp_chain(self, chain, prior=False):

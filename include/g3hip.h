@@ -416,6 +416,27 @@ int g3_gp_dlogp_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, int
                                int64_t ldx, int d, const void* L_dev, int64_t ldl, int64_t kstride, const void* invd_dev,
                                const void* a_dev, g3_dtype dt, void* Y_dev, void* Kinv_dev, void* alpha_dev, double* out_host);
 
+/* ---- leave-one-out predictions from the factor (no counterpart in the reference: its scores / Experiment harness,
+ * g3py/bayesian/models.py:449-469, refits per hold-out split) -------------------------------------------------------------
+ * After g3_gp_factor on the same buffers (L_dev = its K_dev, invd_dev, a_dev = L^-1 delta), for K the factored covariance:
+ *     alpha[i] = [K^-1 delta]_i = sum_j Y_ij a_j        kdiag[i] = [K^-1]_ii = sum_j Y_ij^2        Y = L^-T
+ * so that observation i, predicted from all the others, is N(z_i - alpha_i / kdiag_i, 1 / kdiag_i) in the latent space
+ * (z = T^-1(y); noise included).  Y_dev (roundup(N,128)-square workspace, leading dimension ldy) receives L^-T by the first
+ * half of g3_potri's sweep -- N^3 / 3 flops, the K^-1 product is not run -- and one pass over its upper triangle (nothing
+ * left of the diagonal is read) writes alpha_dev and kdiag_dev, roundup(N,128) entries each, the entries from N on as 0.
+ * The partial sums are combined in a fixed order (bitwise reproducible).  Stream-ordered, no host synchronisation. */
+int g3_gp_loo(g3_ctx* ctx, const void* L_dev, int64_t N, int64_t ldl, const void* invd_dev, const void* a_dev, g3_dtype dt,
+              void* Y_dev, int64_t ldy, void* alpha_dev, void* kdiag_dev);
+/* The same for every member of a chain, after g3_gp_factor_batched(_fields) with the same member layout (factors kstride
+ * elements apart in L_dev with leading dimension ldl, block inverses roundup(N,128)*128 apart, a_dev batch x roundup(N,128));
+ * alpha_dev and kdiag_dev are batch x roundup(N,128).  N <= 256: ONE launch, one workgroup per member -- the member's whole
+ * L^-1 is its two block inverses and V21 = -W1 L21 W0, formed on the MFMA pipe, and alpha / kdiag are its column sums; Y_dev is
+ * not used and may be NULL.  N > 256: the members go through g3_gp_loo one at a time inside this call, Y_dev being one
+ * roundup(N,128)-square workspace.  A member that went through the jitter schedule or the fallback is inverted as it was
+ * kept.  batch <= 4096. */
+int g3_gp_loo_batched(g3_ctx* ctx, int batch, const void* L_dev, int64_t N, int64_t ldl, int64_t kstride, const void* invd_dev,
+                      const void* a_dev, g3_dtype dt, void* Y_dev, void* alpha_dev, void* kdiag_dev);
+
 /* g3_gp_cross for every member of a chain, after ONE g3_gp_factor_batched(_fields) call with the same member layout
  * (factors kstride elements apart in L_dev with leading dimension ldl, block inverses roundup(N,128)*128 apart, a_dev batch
  * x roundup(N,128)): what the reference's average / particles loop over the rows of a trace for
