@@ -66,6 +66,13 @@ def tt_to_cov(c, device=None):
     return dev.download(a)
 
 
+def to_num(a, dtype):
+    """tt_to_num (tensors.py:90-92) as host arithmetic on vectors the device returned: NaN -> 0, +-Inf -> 1e10 (the
+    float32 constant of the reference), the rest as it is, in `dtype`"""
+    big = np.dtype(dtype).type(np.float32(1e10))
+    return np.where(np.isnan(a), 0, np.where(np.isinf(a), big, a))
+
+
 def tt_to_bounded(r, lower=None, upper=None):
     """clamp (tensors.py:101-108); O(n) host arithmetic on vectors the device returned"""
     r = np.asarray(r)

@@ -11,6 +11,7 @@ import numpy as np
 
 from .. import _lib
 from ..device import Device, compile_spec
+from ..libs.tensors import to_num
 from .hypers import HyperVar
 from .hypers.kernels import Kernel, KernelSum, KernelNoise
 from .hypers.means import Mean
@@ -140,6 +141,20 @@ class EllipticalProcess(StochasticProcess):
     def _prog(self, kernel, values, d):
         return compile_spec(kernel.spec(values, d), d)
 
+    def _delta(self, values, X, y, B=None):
+        """(mapped, mu, delta, det_m) = (T^-1(y), m(X), T^-1(y) - m(X), log det dT^-1(y)) in the process dtype
+        (elliptical.py:63; gaussian.py:208, 225) for one row of hyper values -- (N,), (N,), (N,), scalar -- or, with B, for
+        the B rows of a chain block: (B, N) and (B,).  Nothing is scrubbed here: logp sends a non-finite row to its -1e30
+        branch, the posterior works on tt_to_num(mapped); the caller picks."""
+        m, loc = self.f_mapping, self.f_location
+        with np.errstate(all='ignore'):
+            if B is None:
+                mapped, mu, det_m = m.inv(y, values), loc(X, values), m.logdet_dinv(y, values)
+            else:
+                mapped, mu, det_m = m.inv_rows(y, values, B), loc.rows(X, values, B), m.logdet_dinv_rows(y, values, B)
+            mapped, mu = np.asarray(mapped, dtype=self.dtype), np.asarray(mu, dtype=self.dtype)
+            return mapped, mu, mapped - mu, np.asarray(det_m, dtype=self.dtype)[()]
+
     def _factor(self, values, inputs, outputs):
         """L = cholesky_robust(tt_to_cov(K_noise(X, X))), a = L^-1 (T^-1(y) - m(X)) on the device
         (elliptical.py:63,68,71; gaussian.py:208-212, 251-260), cached across statistics."""
@@ -151,13 +166,8 @@ class EllipticalProcess(StochasticProcess):
             return c
         dev = self.device
         N, d = X.shape
-        with np.errstate(all='ignore'):
-            mapped = np.asarray(self.f_mapping.inv(y, values), dtype=self.dtype)      # elliptical.py:63
-            mu = self.f_location(X, values)
-            delta = mapped - mu                                                       # gaussian.py:208
-            det_m = self.f_mapping.logdet_dinv(y, values)                             # gaussian.py:225
-        # tt_to_num(mapping.inv(outputs)) is what the posterior uses (elliptical.py:63)
-        mapped_num = np.where(np.isnan(mapped), 0, np.where(np.isinf(mapped), self.dtype.type(np.float32(1e10)), mapped))
+        mapped, mu, delta, det_m = self._delta(values, X, y)
+        mapped_num = to_num(mapped, self.dtype)      # tt_to_num(mapping.inv(outputs)) is what the posterior uses (elliptical.py:63)
         Np = _lib.roundup(N)
         # device workspace: re-used while the observations stay the same (optimisers and samplers call
         # logp / dlogp thousands of times on one data set -- hipMalloc and the upload of X would
@@ -263,7 +273,7 @@ class EllipticalProcess(StochasticProcess):
         dev.gram_diag(self._prog(kern, values, d), Sd, d, out)
         dg = dev.download(out, 1, M)[0]
         if noise:   # tt_to_cov acts on the whole matrix; its effect on the diagonal:
-            dg = np.where(np.isnan(dg), 0, np.where(np.isinf(dg), self.dtype.type(np.float32(1e10)), dg))
+            dg = to_num(dg, self.dtype)
             m = dg.min()
             if not m > 0:
                 dg = dg + (self.dtype.type(np.float32(1e-6)) - m)
@@ -294,13 +304,13 @@ class EllipticalProcess(StochasticProcess):
         values, _ = self._values(params)
         with np.errstate(all='ignore'):
             r = np.asarray(self.f_mapping.inv(np.asarray(outputs, dtype=self.dtype), values))
-        return np.where(np.isnan(r), 0, np.where(np.isinf(r), self.dtype.type(np.float32(1e10)), r))
+        return to_num(r, self.dtype)
 
     def th_mapping(self, space, inputs, outputs, vector, params, prior=False, noise=False):
         values, _ = self._values(params)
         with np.errstate(all='ignore'):
             r = np.asarray(self.f_mapping(np.asarray(outputs, dtype=self.dtype), values))
-        return np.where(np.isnan(r), 0, np.where(np.isinf(r), self.dtype.type(np.float32(1e10)), r))
+        return to_num(r, self.dtype)
 
     def th_location(self, space, inputs, outputs, vector, params, prior=False, noise=False):
         values, _ = self._values(params)

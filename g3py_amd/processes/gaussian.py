@@ -4,28 +4,32 @@ from scipy import stats
 
 from .. import _lib
 from ..device import compile_spec_rows
+from ..libs.tensors import to_num
 from .elliptical import EllipticalProcess, SENTINEL
 
 
-def logp_cho_diag(value, mu, sd, mapping, values, dtype):
-    """WarpedGaussianDistribution.logp_cho with a DIAGONAL factor (gaussian.py:42-54,192-241):
-    independent marginals, O(M) host arithmetic on device-produced vectors.  (loo_assemble below holds the same density
-    and the same -1e30 conditions for B rows of hyper values at once: change the two together.)"""
+def _logp_diag(delta, sd, det_m, dtype):
+    """log density of independent normal marginals with a DIAGONAL factor `sd` at latent residuals `delta`, plus the
+    warp's log-Jacobian `det_m` (WarpedGaussianDistribution.logp_cho, gaussian.py:42-54, 192-241): the sum over the last
+    axis, so (N,) arguments give a scalar and the (B, N) rows of a chain block (B,).  A row with a non-finite delta,
+    det_m, sd or delta / sd takes the constant -1e30 (gaussian.py:234-241)."""
     t = np.dtype(dtype).type
+    with np.errstate(all='ignore'):
+        lcho = delta / sd
+        r = (t(-0.5) * t(sd.shape[-1]) * np.log(t(2.0 * np.pi)) + t(-0.5) * (lcho * lcho).sum(axis=-1)
+             - np.log(sd).sum(axis=-1) + det_m)
+    bad = ~(np.isfinite(delta).all(axis=-1) & np.isfinite(det_m) & np.isfinite(sd).all(axis=-1) & np.isfinite(lcho).all(axis=-1))
+    return np.where(bad, t(SENTINEL), r).astype(dtype)[()]
+
+
+def logp_cho_diag(value, mu, sd, mapping, values, dtype):
+    """_logp_diag of the observations `value` under independent latent N(mu, sd^2) marginals: O(M) host arithmetic on
+    device-produced vectors"""
     value = np.asarray(value, dtype=dtype)
     with np.errstate(all='ignore'):
         delta = np.asarray(mapping.inv(value, values)) - mu
-        if np.any(~np.isfinite(delta)):
-            return t(SENTINEL)
         det_m = mapping.logdet_dinv(value, values)
-        if np.any(~np.isfinite(det_m)) or np.any(~np.isfinite(sd)):
-            return t(SENTINEL)
-        lcho = delta / sd
-        r = (t(-0.5) * t(len(sd)) * np.log(t(2.0 * np.pi)) + t(-0.5) * lcho.dot(lcho)
-             - np.sum(np.log(sd)) + det_m)
-    if np.any(~np.isfinite(lcho)):
-        return t(SENTINEL)
-    return r
+    return _logp_diag(delta, np.asarray(sd), det_m, dtype)
 
 
 def gauss_hermite(f, mu, sigma, n, dtype):
@@ -48,9 +52,9 @@ def loo_assemble(alpha, kdiag, z, mapping, values, y=None, dtype=np.float64, her
     the warped process's n-point Gauss-Hermite moments, gaussian.py:127-157) -- plus `logpredictive` =
     logp_cho_diag(y, loc, sd, ...), the summed log density of every y_i under its own leave-one-out predictive.
     Two-dimensional alpha / kdiag / z (rows of a chain, `values` from _values_rows): only `logpredictive`, one per row --
-    logp_cho_diag's density and sentinel conditions as array passes over the rows, with z = mapping.inv_rows(y) as the
-    caller has it (NOT scrubbed: a row with a non-finite entry takes the sentinel) and the mapping's logdet_dinv_rows;
-    the curve switches and `hermite` play no part there.  No device, no process: a pure function of its arguments."""
+    logp_cho_diag's _logp_diag over the rows, with z = mapping.inv_rows(y) as the caller has it (NOT scrubbed: a row with
+    a non-finite entry takes the sentinel) and the mapping's logdet_dinv_rows; the curve switches and `hermite` play no
+    part there.  No device, no process: a pure function of its arguments."""
     from ..libs import DictObj
     t = np.dtype(dtype).type
     alpha, kdiag, z = (np.asarray(v, dtype=dtype) for v in (alpha, kdiag, z))
@@ -59,15 +63,9 @@ def loo_assemble(alpha, kdiag, z, mapping, values, y=None, dtype=np.float64, her
         sd = t(1) / np.sqrt(kdiag)
     out = DictObj()
     if alpha.ndim == 2:
-        B, N = alpha.shape
-        yv = np.asarray(y, dtype=dtype)
-        with np.errstate(all='ignore'):           # logp_cho_diag, row by row of the chain
-            delta = z - loc
-            det_m = np.asarray(mapping.logdet_dinv_rows(yv, values, B), dtype=dtype)
-            lcho = delta / sd
-            r = (t(-0.5) * t(N) * np.log(t(2.0 * np.pi)) + t(-0.5) * (lcho * lcho).sum(axis=1) - np.log(sd).sum(axis=1) + det_m)
-        bad = ~(np.isfinite(delta).all(axis=1) & np.isfinite(det_m) & np.isfinite(sd).all(axis=1) & np.isfinite(lcho).all(axis=1))
-        out['logpredictive'] = np.where(bad, t(SENTINEL), r).astype(dtype)
+        det_m = np.asarray(mapping.logdet_dinv_rows(np.asarray(y, dtype=dtype), values, len(alpha)), dtype=dtype)
+        with np.errstate(all='ignore'):
+            out['logpredictive'] = _logp_diag(z - loc, sd, det_m, dtype)
         return out
     with np.errstate(all='ignore'):
         if hermite is None:
@@ -100,13 +98,29 @@ class _Refs(dict):
         return _Ref(name)
 
 
-class GaussianProcess(EllipticalProcess):
-    def __init__(self, *args, **kwargs):
-        if 'name' not in kwargs:
-            kwargs['name'] = 'GP'
-        super().__init__(*args, **kwargs)
+class FactorLikelihood:
+    """What every elliptical process with a density of the Cholesky factor's two scalars shares -- logp, its gradient and
+    their forms over the rows of a chain: mixed into GaussianProcess and StudentTProcess, which supply `_density` and
+    `_dlogp_scale`.  Each host formula below is written once, for a scalar / (N,) vector of one hyper-parameter vector or
+    the (B,) / (B, N) arrays of a chain block alike (reductions over the last axis); only the device calls differ."""
 
-    # ---- log marginal likelihood (gaussian.py:192-249; stochastic.py:300-313)
+    def _nu(self, values, B=None):
+        """degrees of freedom of the density for one row of values, or (B,) for a chain block (None: it has none)"""
+        if self.f_degree is None:
+            return None
+        return self.f_degree(values) if B is None else self.f_degree.rows(values, B)
+
+    def _density(self, logdet, quad, det_m, N, nu):
+        """the observed log-density from the factor's scalars -- logdet = sum log L_ii, quad = |L^-1 delta|^2 -- and the
+        warp's log-Jacobian, as scalars or (B,) arrays, evaluated in the process dtype"""
+        raise NotImplementedError
+
+    def _dlogp_scale(self, nu, quad, N, nat, ok=None):
+        """s in d logp / d quad = -s / 2, as a scalar or (B,) like its arguments (None: s = 1, the Gaussian density); a
+        density with hypers of its own adds their gradient terms to `nat` here (rows with ok False: none)"""
+        return None
+
+    # ---- log marginal likelihood (gaussian.py:192-249, studentT.py:114-146; stochastic.py:300-313)
     def th_loglike(self, space, inputs, outputs, vector, params, prior=False, noise=False):
         values, _ = self._values(params)
         t = self.dtype.type
@@ -119,9 +133,8 @@ class GaussianProcess(EllipticalProcess):
         # cond3 (:236): a factor from a scrubbed covariance (or the 1e-10*I fallback) is finite
         if not np.isfinite(st['logdet']) or st['nonfinite'] > 0:    # cond4, :237
             return t(SENTINEL)
-        n = c['N']
-        npi = t(-0.5) * t(n) * np.log(t(2.0 * np.pi))               # :218
-        return t(npi + t(-0.5) * t(st['quad']) - t(st['logdet']) + c['det_m'])   # :219-232
+        with np.errstate(all='ignore'):
+            return t(self._density(st['logdet'], st['quad'], c['det_m'], c['N'], self._nu(values)))
 
     # ---- gradient of logp (stochastic.py:308-309; tensors.py:11-22, 224-260)
     def th_dlogp(self, space, inputs, outputs, vector, params, prior=False, noise=False):
@@ -140,9 +153,6 @@ class GaussianProcess(EllipticalProcess):
                 self._dloglike(values, inputs, outputs, nat)
         return self._flat_gradient(values, nat)
 
-    def _dlogp_scale(self, values, c, st, nat):
-        return 1.0
-
     def _dloglike(self, values, inputs, outputs, nat):
         """adds d loglike / d (natural-space hyper) into `nat`"""
         dev = self.device
@@ -159,7 +169,8 @@ class GaussianProcess(EllipticalProcess):
         N, d, Np = c['N'], c['d'], c['Np']
         # d logp / d beta = -s / 2 with beta = |L^-1 delta|^2: s = 1 for the Gaussian density; the
         # Student-t density supplies its own s (and its degrees-of-freedom term) through the hook
-        s = float(self._dlogp_scale(values, c, st, nat))
+        s = self._dlogp_scale(self._nu(values), st['quad'], N, nat)
+        s = 1.0 if s is None else float(s)
         if c.get('grad') is None and ds is not None:
             # K^-1 never exists in one place: gathered panels of L^-T, the rank's rows of K^-1, one all-reduce of the sums
             prog, gmap, slots, alpha = ds['dgp'].dlogp(self.f_kernel_noise.spec(values, d), c['Xd'], np.sqrt(s))
@@ -180,14 +191,33 @@ class GaussianProcess(EllipticalProcess):
             c['grad'] = dict(prog=prog, gmap=gmap, slots=slots,
                              alpha=np.sqrt(s) * dev.download(alpha, 1, N)[0].astype(np.float64))
         g = c['grad']
-        self._chain_rule(values, inputs, outputs, nat, g['prog'], g['gmap'], g['slots'], g['alpha'], d)
+        self._chain_rule(values, c['X'], c['y'], nat, g['prog'], g['gmap'], g['slots'], g['alpha'], d)
 
-    def _chain_rule(self, values, inputs, outputs, nat, prog, gmap, slots, alpha, d):
-        """host part of d loglike: route the device's per-leaf parameter sums (`slots`) to the model's
-        variables and add the O(N) location / warping terms on alpha = s K^-1 delta"""
+    def _potential_gradient(self, values, B=None):
+        """the natural-space gradient every evaluation starts from: the L1 / L2 potentials' (hypers/__init__.py:97-109),
+        zeros elsewhere -- {name: v.shape} for one row of values, {name: (B, *v.shape)} for a chain block"""
+        lead = () if B is None else (B,)
+        nat = {v.name: np.zeros(lead + tuple(v.shape)) for v in self.model.vars}
+        for _, reg, c, sel in self.model.potentials:
+            for h in sel:
+                hv = np.asarray(values[h.name], dtype=np.float64)
+                nat[h.name] = nat[h.name] + (-c * np.sign(hv) if reg == 'L1' else -2.0 * c * hv)
+        return nat
+
+    def _chain_rule(self, values, X, y, nat, prog, gmap, slots, alpha, d, ok=None):
+        """host part of d loglike: route the device's per-leaf parameter sums (`slots`) to the model's variables and add
+        the O(N) location / warping terms on alpha = s K^-1 delta.  slots (nslots,) and alpha (N,) for one row of values,
+        (B, nslots) and (B, N) for a chain block; rows with ok False get no likelihood term"""
         from ..device import spec_leaves, LEAF_FIELDS as fields
-        # kernel hypers: leaf parameter slots -> the HyperVars that fed them (the alpha slot of a dot leaf is its bias)
         by_name = {v.name: v for v in self.model.vars}
+        lead = alpha.shape[:-1]
+        if ok is not None:
+            with np.errstate(all='ignore'):
+                slots, alpha = np.where(ok[:, None], slots, 0.0), np.where(ok[:, None], alpha, 0.0)
+
+        def add(name, g):            # g: lead for a scalar hyper, lead + (size,) otherwise
+            nat[name] = nat[name] + (g if np.shape(g) == nat[name].shape else np.reshape(g, nat[name].shape))
+        # kernel hypers: leaf parameter slots -> the HyperVars that fed them (the alpha slot of a dot leaf is its bias)
         refs = spec_leaves(self.f_kernel_noise.spec(_Refs(), d))
         for l, lf in enumerate(refs):
             nd = prog.leaf[l].ndims
@@ -197,53 +227,42 @@ class GaussianProcess(EllipticalProcess):
                     continue
                 slot = getattr(gmap, pname)[l]
                 if pname in ('var', 'alpha'):
-                    nat[ref.name] = nat[ref.name] + slots[slot]
+                    add(ref.name, slots[..., slot])
                 else:
-                    gk = slots[slot:slot + nd]
-                    nat[ref.name] = nat[ref.name] + (gk if by_name[ref.name].shape else gk.sum())
-        # location and warping hypers: O(N) host arithmetic on alpha = K^-1 delta
-        X = self._x(inputs)
-        y = np.asarray(outputs, dtype=self.dtype).reshape(-1)
-        for h, J in self.f_location.grad(X, values):
-            if getattr(h, 'name', None) in by_name:
-                gj = alpha.dot(np.asarray(J, dtype=np.float64))
-                nat[h.name] = nat[h.name] + (gj.reshape(by_name[h.name].shape) if by_name[h.name].shape else gj.sum())
-        with np.errstate(all='ignore'):
-            for h, dinv, dlogdet in self.f_mapping.grad(y, values):
+                    gk = slots[..., slot:slot + nd]
+                    add(ref.name, gk if by_name[ref.name].shape else gk.sum(axis=-1))
+        # location: alpha . d m / d hyper.  Over a chain block d m / d hyper is the same for every row for the means on the
+        # path (linear in their hypers, JAC_CONSTANT); any other mean is asked row by row
+        if not lead or getattr(self.f_location, 'JAC_CONSTANT', False):
+            for h, J in self.f_location.grad(X, self._values_row(values, 0) if lead else values):
                 if getattr(h, 'name', None) in by_name:
-                    nat[h.name] = nat[h.name] + (-alpha.dot(np.asarray(dinv, dtype=np.float64)) + float(dlogdet))
+                    gj = alpha.dot(np.asarray(J, dtype=np.float64))            # lead + (size,)
+                    add(h.name, gj if by_name[h.name].shape else gj.sum(axis=-1))
+        else:
+            for j in range(lead[0]):
+                for h, J in self.f_location.grad(X, self._values_row(values, j)):
+                    if getattr(h, 'name', None) in by_name:
+                        gj = alpha[j].dot(np.asarray(J, dtype=np.float64))
+                        nat[h.name][j] = nat[h.name][j] + (gj.reshape(by_name[h.name].shape) if by_name[h.name].shape else gj.sum())
+        # warping: -alpha . d T^-1(y) / d hyper + d logdet / d hyper
+        with np.errstate(all='ignore'):
+            for h, dinv, dlogdet in (self.f_mapping.grad_rows(y, values, lead[0]) if lead else self.f_mapping.grad(y, values)):
+                if getattr(h, 'name', None) in by_name:
+                    g = -(alpha * np.asarray(dinv, dtype=np.float64)).sum(axis=-1) + np.asarray(dlogdet, dtype=np.float64)
+                    add(h.name, g if ok is None else np.where(ok, g, 0.0))
 
-    def _flat_gradient(self, values, nat):
-        """natural-space gradients -> flat vector in creation order, transformed space, tt_to_num'ed"""
+    def _flat_gradient(self, values, nat, B=None):
+        """natural-space gradients -> flat vector in creation order, transformed space, tt_to_num'ed: (ndim,), or
+        (B, ndim) for a chain block"""
+        lead = () if B is None else (B,)
         flat = []
         for v in self.model.vars:
-            g = np.asarray(nat[v.name], dtype=np.float64).reshape(v.shape)
+            g = np.asarray(nat[v.name], dtype=np.float64).reshape(lead + (-1,))
             if v.positive:
-                g = g * np.asarray(values[v.name], dtype=np.float64)
-            flat.append(g.reshape(-1))
-        flat = np.concatenate(flat) if flat else np.zeros(0)
-        flat = np.where(np.isnan(flat), 0.0, np.where(np.isinf(flat), float(np.float32(1e10)), flat))   # tt_to_num
-        return flat.astype(self.dtype)
-
-    def _potential_gradient(self, values):
-        nat = {v.name: np.zeros(v.shape, dtype=np.float64) for v in self.model.vars}
-        for _, reg, c, sel in self.model.potentials:                # hypers/__init__.py:97-109
-            for h in sel:
-                hv = np.asarray(values[h.name], dtype=np.float64)
-                nat[h.name] = nat[h.name] + (-c * np.sign(hv) if reg == 'L1' else -2.0 * c * hv)
-        return nat
-
-    def _chain_density(self, values_b, st, det_m, N, B):
-        """the rows' observed log-density from the device statistics st = [logdet, quad, ...] (B, 6): the Gaussian
-        -n/2 log 2 pi - beta/2 - sum log L_ii + logdet_dinv (gaussian.py:208-224), evaluated in the process dtype"""
-        t = self.dtype.type
-        npi = t(-0.5) * t(N) * np.log(t(2.0 * np.pi))
-        return npi + t(-0.5) * st[:, 1].astype(self.dtype) - st[:, 0].astype(self.dtype) + det_m
-
-    def _chain_dlogp_scale(self, values_b, st, N, nat, ok, B):
-        """rows' s in d logp / d beta = -s / 2 (None: the Gaussian's s = 1); a density with its own hypers adds their
-        gradient terms to `nat` here (rows with ok False: none)"""
-        return None
+                g = g * np.asarray(values[v.name], dtype=np.float64).reshape(lead + (-1,))
+            flat.append(g)
+        flat = np.concatenate(flat, axis=-1) if flat else np.zeros(lead + (0,))
+        return to_num(flat, np.float64).astype(self.dtype)
 
     def _chain_workspace(self, batch, Np, grad, pred=0):
         """device buffers of logp_chain / dlogp_chain / predict_chain, kept between calls (samplers and optimisers evaluate
@@ -304,44 +323,10 @@ class GaussianProcess(EllipticalProcess):
         differ per row (compile_spec_rows)"""
         return compile_spec_rows(kern.spec(values_b, d), kern.spec(self._values_row(values_b, 0), d), d, B)
 
-    # ---- posterior prediction over a chain (models.py:489-519: a loop of single predictions in the reference)
-    _CHAIN_PREDICT = True
-
-    def _chain_predict_batched(self):
-        """the batched block path serves the plain Gaussian process on one GPU: a warping needs its row form of the
-        forward map and of the Gauss-Hermite moments, the Student-t process its per-row scale, a distributed process the
-        multi-GPU driver -- those take the loop of single predictions"""
-        from .hypers.mappings import Identity
-        return bool(type(self)._CHAIN_PREDICT and self._dist is None and type(self.f_mapping) is Identity)
-
-    def _chain_block_members(self, rows_b, kern, S, X, y, prior):
-        """what one block of chain rows hands the batched entry points: the rows' values, the members of `kern` (the
-        cross / prior kernel) as template + fields, the rows' location at the query points S and -- a posteriori -- the
-        members of the observation kernel with the rows' delta = tt_to_num(mapping.inv(y)) - m(X) (elliptical.py:63),
-        non-finite entries sent as 0, exactly as _factor / _solve('post') prepare it for one row"""
-        B, d = len(rows_b), S.shape[1]
-        big = self.dtype.type(np.float32(1e10))
-        values_b, _ = self._values_rows(rows_b)
-        members = self._chain_members(kern, values_b, d, B)
-        with np.errstate(all='ignore'):
-            loc = np.asarray(self.f_location.rows(S, values_b, B), dtype=self.dtype)
-        if prior:
-            return values_b, members, loc, None, None
-        obs = self._chain_members(self.f_kernel_noise, values_b, d, B)
-        with np.errstate(all='ignore'):
-            mapped = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
-            mapped = np.where(np.isnan(mapped), 0, np.where(np.isinf(mapped), big, mapped))
-            delta = mapped - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype)
-        delta = np.where(np.isfinite(delta), delta, 0).astype(self.dtype)
-        return values_b, members, loc, obs, delta
-
     def _chain_delta_or_bad(self, values_b, X, y, B):
         """the logp / dlogp rows' (delta, logdet_dinv, bad): a row with a non-finite entry takes the constant -1e30 branch
         (gaussian.py:234-235); it is evaluated like the others on zeros, and its result replaced by the caller"""
-        with np.errstate(all='ignore'):
-            delta = (np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
-                     - np.asarray(self.f_location.rows(X, values_b, B), dtype=self.dtype))
-            det_m = np.asarray(self.f_mapping.logdet_dinv_rows(y, values_b, B), dtype=self.dtype)
+        _, _, delta, det_m = self._delta(values_b, X, y, B)
         bad = ~(np.isfinite(delta).all(axis=1) & np.isfinite(det_m))
         if bad.any():
             delta = np.where(bad[:, None], self.dtype.type(0), delta)
@@ -359,6 +344,124 @@ class GaussianProcess(EllipticalProcess):
         finally:
             dd.free()         # a (B, N) buffer per block: not left to the garbage collector over a long chain
 
+    def dlogp_chain(self, chain, batch=None):
+        """one dlogp per row of a flat-parameter chain, shape (rows, ndim) -- what fixed_dlogp averages
+        (stochastic.py:554-564: a loop of single gradients in the reference).  `batch` rows at a time
+        share ONE Gram launch, ONE factorisation sweep (g3_gp_factor_batched_fields) and ONE K^-1 sweep with the
+        members' alpha and kernel-parameter sums in launches that carry the member in grid.y
+        (g3_gp_dlogp_batched_fields); the O(N) chain-rule pieces are array arithmetic over the rows on the host."""
+        chain = np.atleast_2d(np.asarray(chain, dtype=np.float64))
+        n_rows = len(chain)
+        out = np.zeros((n_rows, self.active.ndim), dtype=self.dtype)
+        if not self.is_observed or n_rows == 0:
+            for i in range(n_rows):
+                out[i] = self.dlogp(chain[i], array=True)
+            return out
+        dev = self.device
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+            n_rows, batch, lambda Np, kstride: int(4e9 // (3 * kstride * self.dtype.itemsize)), grad=True)
+        K, Y, Ki, W, a, al = ws['K'], ws['Y'], ws['Ki'], ws['W'], ws['a'], ws['al']
+        for lo in range(0, n_rows, batch):
+            hi = min(lo + batch, n_rows)
+            B = hi - lo
+            # the block's host side in NumPy passes over all rows (as logp_chain): values, programs as template + fields,
+            # warped observations, mean; the device then does factor, K^-1, alpha and the kernel-parameter sums of every
+            # member in batched launches, and the chain rule below is array arithmetic over the rows
+            values_b, _ = self._values_rows(chain[lo:hi])
+            tmpl, offs, fields = members = self._chain_members(self.f_kernel_noise, values_b, d, B)
+            delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
+            st = self._chain_factor_block(members, delta, Xd, N, d, K, kstride, W, a)
+            gmap = dev.grad_layout(tmpl)
+            ok = ~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0)
+            nat = self._potential_gradient(values_b, B)
+            s = self._dlogp_scale(self._nu(values_b, B), st[:, 1], N, nat, ok)
+            if s is not None:     # G = s alpha alpha^T - K^-1: the device gets sqrt(s) a and returns sqrt(s) alpha
+                with np.errstate(all='ignore'):
+                    rs = np.where(ok, np.sqrt(s), 1.0)
+                dev.copy_in(a, (dev.download(a, B, Np) * rs[:, None].astype(self.dtype)).astype(self.dtype))
+            slots = dev.gp_dlogp_batched_fields(tmpl, offs, fields, gmap, Xd, N, d, K, kstride, W, a, Y, Ki, al)
+            alphas = dev.download(al, B, N).astype(np.float64)
+            if s is not None:
+                alphas = alphas * rs[:, None]
+            self._chain_rule(values_b, X, y, nat, tmpl, gmap, slots, alphas, d, ok)
+            out[lo:hi] = self._flat_gradient(values_b, nat, B)
+        return out
+
+    # ---- many hyper-parameter vectors on the same observations (stochastic.py:515-520)
+    def logp_chain(self, chain, prior=False, batch=None):
+        """one logp per row of a flat-parameter chain.  The reference loops over the rows
+        (stochastic.py:515-520; fixed_logp :526-532, "TODO: Vectorized"); here `batch` rows at a
+        time go through ONE Gram launch and ONE factorisation sweep (g3_gp_factor_batched), which
+        is what fills the GPU when a single N x N problem is too small to.  `batch` defaults to
+        as many members as fit in 4 GB of covariance workspace."""
+        chain = np.atleast_2d(np.asarray(chain, dtype=np.float64))
+        n_rows = len(chain)
+        t = self.dtype.type
+        out = np.empty(n_rows, dtype=self.dtype)
+        if prior or not self.is_observed or n_rows == 0:
+            if n_rows:                      # the free variables' terms only (th_logp with prior=True): no device work
+                out[:] = self._values_rows(chain)[1].astype(self.dtype)
+            return out
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+            n_rows, batch, lambda Np, kstride: int(4e9 // (kstride * self.dtype.itemsize)))
+        K, W, a = ws['K'], ws['W'], ws['a']
+        for lo in range(0, n_rows, batch):
+            hi = min(lo + batch, n_rows)
+            B = hi - lo
+            # the whole block at once on the host: values, programs (one template + the hyper values that differ per
+            # row), warped observations and the mean -- O(B) NumPy passes, no per-row Python
+            values_b, logjac = self._values_rows(chain[lo:hi])
+            delta, det_m, bad = self._chain_delta_or_bad(values_b, X, y, B)
+            st = self._chain_factor_block(self._chain_members(self.f_kernel_noise, values_b, d, B), delta, Xd, N, d, K, kstride, W, a)
+            with np.errstate(all='ignore'):
+                lp = logjac.astype(self.dtype) + np.asarray(
+                    self._density(st[:, 0], st[:, 1], det_m, N, self._nu(values_b, B)), dtype=self.dtype)
+            bad |= ~np.isfinite(st[:, 0]) | (st[:, 2] > 0)                                # gaussian.py:237
+            out[lo:hi] = np.where(bad, logjac.astype(self.dtype) + t(SENTINEL), lp)
+        return out
+
+
+class GaussianProcess(FactorLikelihood, EllipticalProcess):
+    def __init__(self, *args, **kwargs):
+        if 'name' not in kwargs:
+            kwargs['name'] = 'GP'
+        super().__init__(*args, **kwargs)
+
+    def _density(self, logdet, quad, det_m, N, nu=None):
+        """-n/2 log 2 pi - quad / 2 - sum log L_ii + logdet_dinv (gaussian.py:208-232)"""
+        t = self.dtype.type
+        npi = t(-0.5) * t(N) * np.log(t(2.0 * np.pi))               # :218
+        return npi + t(-0.5) * np.asarray(quad, dtype=self.dtype) - np.asarray(logdet, dtype=self.dtype) + det_m   # :219-232
+
+    # ---- posterior prediction over a chain (models.py:489-519: a loop of single predictions in the reference)
+    _CHAIN_PREDICT = True
+
+    def _chain_predict_batched(self):
+        """the batched block path serves the plain Gaussian process on one GPU: a warping needs its row form of the
+        forward map and of the Gauss-Hermite moments, the Student-t process its per-row scale, a distributed process the
+        multi-GPU driver -- those take the loop of single predictions"""
+        from .hypers.mappings import Identity
+        return bool(type(self)._CHAIN_PREDICT and self._dist is None and type(self.f_mapping) is Identity)
+
+    def _chain_block_members(self, rows_b, kern, S, X, y, prior):
+        """what one block of chain rows hands the batched entry points: the rows' values, the members of `kern` (the
+        cross / prior kernel) as template + fields, the rows' location at the query points S and -- a posteriori -- the
+        members of the observation kernel with the rows' delta = tt_to_num(mapping.inv(y)) - m(X) (elliptical.py:63),
+        non-finite entries sent as 0, exactly as _factor / _solve('post') prepare it for one row"""
+        B, d = len(rows_b), S.shape[1]
+        values_b, _ = self._values_rows(rows_b)
+        members = self._chain_members(kern, values_b, d, B)
+        with np.errstate(all='ignore'):
+            loc = np.asarray(self.f_location.rows(S, values_b, B), dtype=self.dtype)
+        if prior:
+            return values_b, members, loc, None, None
+        obs = self._chain_members(self.f_kernel_noise, values_b, d, B)
+        mapped, mu, _, _ = self._delta(values_b, X, y, B)
+        with np.errstate(all='ignore'):
+            delta = to_num(mapped, self.dtype) - mu
+        delta = np.where(np.isfinite(delta), delta, 0).astype(self.dtype)
+        return values_b, members, loc, obs, delta
+
     def _predict_chain_blocks(self, rows, space, inputs, outputs, switches, noise, prior, batch):
         """predict_chain for a plain Gaussian process: per block of `batch` rows ONE batched factorisation
         (g3_gp_factor_batched_fields) and ONE batched cross solve (g3_gp_cross_batched_fields: rectangular Gram with the
@@ -367,7 +470,6 @@ class GaussianProcess(EllipticalProcess):
         from ..libs import DictObj
         dev = self.device
         t = self.dtype.type
-        big = t(np.float32(1e10))
         S = self._x(self.space if space is None else space)
         n_rows, M = len(rows), S.shape[0]
         Mp = _lib.roundup(M, _lib.G3_RHS_PAD)
@@ -410,7 +512,7 @@ class GaussianProcess(EllipticalProcess):
                     if need_var:
                         dg = dev.download(kd, B, M)
                         if noise:   # tt_to_cov acts on the whole matrix; its effect on each row's diagonal
-                            dg = np.where(np.isnan(dg), 0, np.where(np.isinf(dg), big, dg))
+                            dg = to_num(dg, self.dtype)
                             m = dg.min(axis=1)
                             dg = np.where(~(m > 0)[:, None], dg + (t(np.float32(1e-6)) - m)[:, None], dg)
                         if not prior:
@@ -426,7 +528,7 @@ class GaussianProcess(EllipticalProcess):
                             out[k][lo:hi] = sd
                         else:       # quantiler: mapping(location + p * kernel_sd), th_mapping scrubs its result
                             r = loc + (p_up if k == 'quantile_up' else p_down) * sd
-                            out[k][lo:hi] = np.where(np.isnan(r), 0, np.where(np.isinf(r), big, r))
+                            out[k][lo:hi] = to_num(r, self.dtype)
         finally:
             Sd.free()
             if Xd is not Sd:
@@ -442,7 +544,6 @@ class GaussianProcess(EllipticalProcess):
         location and the mapping's scrub, as th_location / th_mapping do for one row.  Returns (draws (rows, M, samples),
         tries, fallback, jitter per row)."""
         dev = self.device
-        big = self.dtype.type(np.float32(1e10))
         S = self._x(self.space if space is None else space)
         n_rows, M = len(rows), S.shape[0]
         samples = rand.shape[2]
@@ -470,150 +571,12 @@ class GaussianProcess(EllipticalProcess):
                 g, tries[lo:hi], fallback[lo:hi], jitter[lo:hi] = dev.gp_draws_batched_fields(
                     tmpl, offs, fields, Sd, M, Xd, N, d, K, kstride, W, a, noise, loc, rand[lo:hi])
                 with np.errstate(all='ignore'):
-                    out[lo:hi] = np.where(np.isnan(g), 0, np.where(np.isinf(g), big, g))     # th_mapping scrubs its result
+                    out[lo:hi] = to_num(g, self.dtype)     # th_mapping scrubs its result
         finally:
             Sd.free()
             if Xd is not None:
                 Xd.free()
         return out, tries, fallback, jitter
-
-    def dlogp_chain(self, chain, batch=None):
-        """one dlogp per row of a flat-parameter chain, shape (rows, ndim) -- what fixed_dlogp averages
-        (stochastic.py:554-564: a loop of single gradients in the reference).  `batch` rows at a time
-        share ONE Gram launch, ONE factorisation sweep (g3_gp_factor_batched_fields) and ONE K^-1 sweep with the
-        members' alpha and kernel-parameter sums in launches that carry the member in grid.y
-        (g3_gp_dlogp_batched_fields); the O(N) chain-rule pieces are array arithmetic over the rows on the host."""
-        chain = np.atleast_2d(np.asarray(chain, dtype=np.float64))
-        n_rows = len(chain)
-        out = np.zeros((n_rows, self.active.ndim), dtype=self.dtype)
-        custom_scale = (type(self)._dlogp_scale is not GaussianProcess._dlogp_scale
-                        and type(self)._chain_dlogp_scale is GaussianProcess._chain_dlogp_scale)
-        if not self.is_observed or n_rows == 0 or custom_scale:
-            for i in range(n_rows):          # a density with a per-member scale and no row form of it: one at a time
-                out[i] = self.dlogp(chain[i], array=True)
-            return out
-        dev = self.device
-        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
-            n_rows, batch, lambda Np, kstride: int(4e9 // (3 * kstride * self.dtype.itemsize)), grad=True)
-        K, Y, Ki, W, a, al = ws['K'], ws['Y'], ws['Ki'], ws['W'], ws['a'], ws['al']
-        for lo in range(0, n_rows, batch):
-            hi = min(lo + batch, n_rows)
-            B = hi - lo
-            # the block's host side in NumPy passes over all rows (as logp_chain): values, programs as template + fields,
-            # warped observations, mean; the device then does factor, K^-1, alpha and the kernel-parameter sums of every
-            # member in batched launches, and the chain rule below is array arithmetic over the rows
-            values_b, _ = self._values_rows(chain[lo:hi])
-            tmpl, offs, fields = members = self._chain_members(self.f_kernel_noise, values_b, d, B)
-            delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
-            st = self._chain_factor_block(members, delta, Xd, N, d, K, kstride, W, a)
-            gmap = dev.grad_layout(tmpl)
-            ok = ~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0)
-            nat = self._potential_gradient_rows(values_b, B)
-            s = self._chain_dlogp_scale(values_b, st, N, nat, ok, B)
-            if s is not None:     # G = s alpha alpha^T - K^-1: the device gets sqrt(s) a and returns sqrt(s) alpha
-                with np.errstate(all='ignore'):
-                    rs = np.where(ok, np.sqrt(s), 1.0)
-                dev.copy_in(a, (dev.download(a, B, Np) * rs[:, None].astype(self.dtype)).astype(self.dtype))
-            slots = dev.gp_dlogp_batched_fields(tmpl, offs, fields, gmap, Xd, N, d, K, kstride, W, a, Y, Ki, al)
-            alphas = dev.download(al, B, N).astype(np.float64)
-            if s is not None:
-                alphas = alphas * rs[:, None]
-            self._chain_rule_rows(values_b, X, y, nat, tmpl, gmap, slots, alphas, d, ok, B)
-            out[lo:hi] = self._flat_gradient_rows(values_b, nat, B)
-        return out
-
-    def _potential_gradient_rows(self, values_b, B):
-        nat = {v.name: np.zeros((B,) + tuple(v.shape)) for v in self.model.vars}
-        for _, reg, c, sel in self.model.potentials:                # hypers/__init__.py:97-109
-            for h in sel:
-                hv = np.asarray(values_b[h.name], dtype=np.float64)
-                nat[h.name] = nat[h.name] + (-c * np.sign(hv) if reg == 'L1' else -2.0 * c * hv)
-        return nat
-
-    def _chain_rule_rows(self, values_b, X, y, nat, prog, gmap, slots, alphas, d, ok, B):
-        """_chain_rule for B rows at once: slots (B, nslots), alphas (B, N); rows with ok False get no likelihood term"""
-        from ..device import spec_leaves, LEAF_FIELDS as fld
-        by_name = {v.name: v for v in self.model.vars}
-        with np.errstate(all='ignore'):
-            slots = np.where(ok[:, None], slots, 0.0)
-            alphas = np.where(ok[:, None], alphas, 0.0)
-
-        def add(name, g):            # g: (B,) for a scalar hyper, (B, size) otherwise
-            shp = tuple(by_name[name].shape)
-            nat[name] = nat[name] + np.asarray(g, dtype=np.float64).reshape((B,) + shp)
-        refs = spec_leaves(self.f_kernel_noise.spec(_Refs(), d))
-        for l, lf in enumerate(refs):
-            nd = prog.leaf[l].ndims
-            for pname, idx in dict(var=1, **fld[lf[0]]).items():
-                ref = lf[idx]
-                if not isinstance(ref, _Ref) or ref.name not in by_name:
-                    continue
-                slot = getattr(gmap, pname)[l]
-                if pname in ('var', 'alpha'):
-                    add(ref.name, slots[:, slot])
-                else:
-                    gk = slots[:, slot:slot + nd]
-                    add(ref.name, gk if by_name[ref.name].shape else gk.sum(axis=1))
-        # location: d m / d hyper is the same for every row for the means on the path (linear in their hypers)
-        if getattr(self.f_location, 'JAC_CONSTANT', False):
-            for h, J in self.f_location.grad(X, self._values_row(values_b, 0)):
-                if getattr(h, 'name', None) in by_name:
-                    gj = alphas.dot(np.asarray(J, dtype=np.float64))           # (B, size)
-                    add(h.name, gj if by_name[h.name].shape else gj.sum(axis=1))
-        else:
-            for j in range(B):
-                for h, J in self.f_location.grad(X, self._values_row(values_b, j)):
-                    if getattr(h, 'name', None) in by_name:
-                        gj = alphas[j].dot(np.asarray(J, dtype=np.float64))
-                        nat[h.name][j] = nat[h.name][j] + (gj.reshape(by_name[h.name].shape) if by_name[h.name].shape else gj.sum())
-        with np.errstate(all='ignore'):
-            for h, dinv, dlogdet in self.f_mapping.grad_rows(y, values_b, B):
-                if getattr(h, 'name', None) in by_name:
-                    g = -(alphas * np.asarray(dinv, dtype=np.float64)).sum(axis=1) + np.asarray(dlogdet, dtype=np.float64)
-                    add(h.name, np.where(ok, g, 0.0))
-
-    def _flat_gradient_rows(self, values_b, nat, B):
-        flat = []
-        for v in self.model.vars:
-            g = np.asarray(nat[v.name], dtype=np.float64).reshape(B, -1)
-            if v.positive:
-                g = g * np.asarray(values_b[v.name], dtype=np.float64).reshape(B, -1)
-            flat.append(g)
-        flat = np.concatenate(flat, axis=1) if flat else np.zeros((B, 0))
-        flat = np.where(np.isnan(flat), 0.0, np.where(np.isinf(flat), float(np.float32(1e10)), flat))   # tt_to_num
-        return flat.astype(self.dtype)
-
-    # ---- many hyper-parameter vectors on the same observations (stochastic.py:515-520)
-    def logp_chain(self, chain, prior=False, batch=None):
-        """one logp per row of a flat-parameter chain.  The reference loops over the rows
-        (stochastic.py:515-520; fixed_logp :526-532, "TODO: Vectorized"); here `batch` rows at a
-        time go through ONE Gram launch and ONE factorisation sweep (g3_gp_factor_batched), which
-        is what fills the GPU when a single N x N problem is too small to.  `batch` defaults to
-        as many members as fit in 4 GB of covariance workspace."""
-        chain = np.atleast_2d(np.asarray(chain, dtype=np.float64))
-        n_rows = len(chain)
-        t = self.dtype.type
-        out = np.empty(n_rows, dtype=self.dtype)
-        if prior or not self.is_observed or n_rows == 0:
-            if n_rows:                      # the free variables' terms only (th_logp with prior=True): no device work
-                out[:] = self._values_rows(chain)[1].astype(self.dtype)
-            return out
-        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
-            n_rows, batch, lambda Np, kstride: int(4e9 // (kstride * self.dtype.itemsize)))
-        K, W, a = ws['K'], ws['W'], ws['a']
-        for lo in range(0, n_rows, batch):
-            hi = min(lo + batch, n_rows)
-            B = hi - lo
-            # the whole block at once on the host: values, programs (one template + the hyper values that differ per
-            # row), warped observations and the mean -- O(B) NumPy passes, no per-row Python
-            values_b, logjac = self._values_rows(chain[lo:hi])
-            delta, det_m, bad = self._chain_delta_or_bad(values_b, X, y, B)
-            st = self._chain_factor_block(self._chain_members(self.f_kernel_noise, values_b, d, B), delta, Xd, N, d, K, kstride, W, a)
-            with np.errstate(all='ignore'):
-                lp = logjac.astype(self.dtype) + self._chain_density(values_b, st, det_m, N, B).astype(self.dtype)
-            bad |= ~np.isfinite(st[:, 0]) | (st[:, 2] > 0)                                # gaussian.py:237
-            out[lo:hi] = np.where(bad, logjac.astype(self.dtype) + t(SENTINEL), lp)
-        return out
 
     def th_logpredictive(self, space, inputs, outputs, vector, params, prior=False, noise=False):
         loc, sd, values = self._loc_sd(space, inputs, outputs, params, prior, noise, sd_noise=True)

@@ -8,6 +8,7 @@ under `<name>_log_` exactly as in the reference's parameter dicts
 """
 import numpy as np
 
+from ...device import Rows
 from ...libs import DictObj
 
 _MODEL_STACK = []
@@ -206,11 +207,11 @@ class Freedom(Hypers):
         return dict(self.default_hypers(x, y))
 
     def __call__(self, values=None):
-        return float(self.bound) + float(np.asarray(value_of(self.degree, values or {})))
+        return float(self.bound) + param(self.degree, values, np.float64)
 
     def rows(self, values_rows, B):
         """nu for B rows of hyper values -> (B,) float64"""
-        return float(self.bound) + np.broadcast_to(np.asarray(value_of(self.degree, values_rows), dtype=np.float64).reshape(-1), (B,))
+        return np.broadcast_to(per_row(self(as_rows(values_rows))), (B,))
 
 
 def value_of(h, values):
@@ -218,3 +219,43 @@ def value_of(h, values):
     if isinstance(h, HyperVar):
         return values[h.name]
     return h
+
+
+def param(h, values, t):
+    """a hyper's value in the working dtype `t`, shaped so that ONE formula serves one hyper-parameter vector and the B
+    rows of a chain block: a plain value or a constant keeps its own shape (a scalar: the NumPy scalar t(value)), a
+    `device.Rows` array gets its row axis in front of the observations' -- (B,) -> (B, 1), a per-column hyper stays
+    (B, ncols).  Expressions that broadcast (N,) observations against such parameters and reduce over axis=-1 give the
+    one-row result or (B, ...) alike."""
+    v = value_of(h, values or {})
+    if isinstance(v, Rows):
+        v = np.asarray(v, dtype=t)
+        return v[:, None] if v.ndim == 1 else v
+    return t(v) if np.ndim(v) == 0 else np.asarray(v, dtype=t)
+
+
+def per_row(p):
+    """a `param` (or an expression of them) where it meets a last-axis reduction: () stays, (B, 1) -> (B,)"""
+    return p[..., 0] if np.ndim(p) else p
+
+
+def as_rows(values_rows):
+    """mark every entry of a {hyper name: (B, ...) array} dict as Rows (what _values_rows returns already is)"""
+    return {k: v if isinstance(v, Rows) else np.asarray(v).view(Rows) for k, v in values_rows.items()}
+
+
+def row_blocks(values_rows, B, n):
+    """(lo, hi, the Rows values of rows lo:hi) over B rows, in blocks whose (rows, n) float64 temporaries are 64 KB: how
+    the `*_rows` forms of a mapping evaluate its one formula.  A formula leaves a dozen temporaries of its result's size
+    behind; at (B, n) = (256, 256) each is 512 KB, which the C allocator takes from the top of the heap and hands back to
+    the system on every call -- and with the HIP runtime in the process the next host-to-device copy then waits 10 ms at
+    a time (profiles/HISTORY.md, "Host side of the processes").  Small blocks stay inside the heap (and the cache)."""
+    step = max(1, 8192 // max(int(n), 1))
+    rows = as_rows(values_rows)
+    for lo in range(0, B, step):
+        yield lo, min(lo + step, B), {k: v[lo:lo + step] for k, v in rows.items()}
+
+
+def each_row(f, x, values_rows, B):
+    """[f(x, values of row j)]: how the `*_rows` forms serve a class that has not declared BROADCASTS"""
+    return [f(x, {k: np.asarray(v)[j] for k, v in values_rows.items()}) for j in range(B)]

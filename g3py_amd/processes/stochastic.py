@@ -267,57 +267,50 @@ class StochasticProcess:
     def hidden(self, value):
         self.np_hidden = value
 
+    def _natural(self, raw, lead):
+        """the one body of _values (lead = ()) and _values_rows (lead = (B,)): natural-space values by hyper name from
+        raw(v), the transformed-space value of variable v shaped lead + v.shape, and the terms every process adds to logp
+        besides the observed density, shaped lead -- the log-Jacobian of the FlatExp variables (hypers/__init__.py:199-200)
+        and the L1 / L2 potentials registered by check_potential (hypers/__init__.py:94-109), which enter th_logp like
+        pm.Potential terms (stochastic.py:305).  Reductions run over a variable's own entries, per row."""
+        values, logjac = {}, np.zeros(lead)
+        with np.errstate(over='ignore'):
+            for v in self.model.vars:
+                p = raw(v)
+                if v.positive:
+                    p = np.exp(p)
+                    logjac = logjac + np.where(p > 1e-6, 0.0, -np.inf).reshape(lead + (-1,)).sum(axis=-1)
+                values[v.name] = p
+        for _, reg, c, sel in self.model.potentials:
+            if reg in ('L1', 'L2'):
+                tot = np.zeros(lead)
+                for h in sel:
+                    hv = np.asarray(values[h.name]).reshape(lead + (-1,))
+                    tot = tot + (np.abs(hv).sum(axis=-1) if reg == 'L1' else (hv ** 2).sum(axis=-1))
+                logjac = logjac + c * -tot
+        return values, logjac
+
     def _values(self, params):
-        """transformed-space params dict -> natural-space values by hyper name, and the terms every
-        process adds to logp besides the observed density: the log-Jacobian of the FlatExp variables
-        (hypers/__init__.py:199-200) and the L1 / L2 potentials registered by check_potential
-        (hypers/__init__.py:94-109; stochastic.py:305).  Shared by the elliptical and the transport
+        """transformed-space params dict -> (natural-space values by hyper name, extra logp terms as a float): _natural
+        for one hyper-parameter vector, remembered per params object.  Shared by the elliptical and the transport
         processes."""
         memo = getattr(self, '_values_memo', None)
         if memo is not None and memo[0] is params:          # th_logp -> th_loglike -> ... share one params object
             return memo[1], memo[2]
-        values, logjac = {}, 0.0
-        for v in self.model.vars:
-            p = np.asarray(params[v.key], dtype=np.float64)
-            if v.positive:
-                with np.errstate(over='ignore'):
-                    e = np.exp(p)
-                logjac += float(np.sum(np.where(e > 1e-6, 0.0, -np.inf)))
-                values[v.name] = e
-            else:
-                values[v.name] = p
-        # optional L1 / L2 potentials enter th_logp like pm.Potential terms (stochastic.py:305)
-        for _, reg, c, sel in self.model.potentials:
-            if reg == 'L1':
-                logjac += c * -float(sum(np.sum(np.abs(values[h.name])) for h in sel))
-            elif reg == 'L2':
-                logjac += c * -float(sum(np.sum(np.asarray(values[h.name]) ** 2) for h in sel))
-        self._values_memo = (params, values, logjac)
-        return values, logjac
+        values, logjac = self._natural(lambda v: np.asarray(params[v.key], dtype=np.float64), ())
+        self._values_memo = (params, values, float(logjac))
+        return values, float(logjac)
 
     def _values_rows(self, chain):
-        """_values for every row of a flat-parameter chain at once: {hyper name: Rows (B, *shape)} and the (B,) extra
-        logp terms.  Same arithmetic as _values, reductions taken per row."""
+        """_natural for every row of a flat-parameter chain at once: {hyper name: Rows (B, *shape)} and the (B,) extra
+        logp terms"""
         from ..device import Rows
         chain = np.asarray(chain, dtype=np.float64)
         B = len(chain)
-        values, logjac, o = {}, np.zeros(B), 0
-        for v in self.model.vars:
-            p = chain[:, o:o + v.size].reshape((B,) + tuple(v.shape))
-            o += v.size
-            if v.positive:
-                with np.errstate(over='ignore'):
-                    p = np.exp(p)
-                logjac = logjac + np.where(p > 1e-6, 0.0, -np.inf).reshape(B, -1).sum(axis=1)
-            values[v.name] = np.ascontiguousarray(p).view(Rows)
-        for _, reg, c, sel in self.model.potentials:
-            tot = np.zeros(B)
-            for h in sel:
-                hv = np.asarray(values[h.name]).reshape(B, -1)
-                tot = tot + (np.abs(hv).sum(axis=1) if reg == 'L1' else (hv ** 2).sum(axis=1))
-            if reg in ('L1', 'L2'):
-                logjac = logjac + c * -tot
-        return values, logjac
+        at = np.cumsum([0] + [v.size for v in self.model.vars])
+        cols = {v.name: slice(at[i], at[i + 1]) for i, v in enumerate(self.model.vars)}
+        values, logjac = self._natural(lambda v: chain[:, cols[v.name]].reshape((B,) + tuple(v.shape)), (B,))
+        return {k: np.ascontiguousarray(p).view(Rows) for k, p in values.items()}, logjac
 
     @staticmethod
     def _values_row(values_rows, j):

@@ -10,12 +10,12 @@ from scipy import stats
 from scipy.special import gammaln, digamma
 
 from .. import _lib
-from .elliptical import EllipticalProcess, SENTINEL
-from .gaussian import GaussianProcess
+from .elliptical import EllipticalProcess
+from .gaussian import FactorLikelihood, gauss_hermite
 from .hypers import Freedom, HyperVar
 
 
-class StudentTProcess(EllipticalProcess):
+class StudentTProcess(FactorLikelihood, EllipticalProcess):
     def __init__(self, *args, **kwargs):
         if 'name' not in kwargs:
             kwargs['name'] = 'TP'
@@ -23,78 +23,37 @@ class StudentTProcess(EllipticalProcess):
             kwargs['degree'] = Freedom()
         super().__init__(*args, **kwargs)
 
-    # ---- log-density (WarpedStudentTDistribution.logp_cho, studentT.py:114-146)
-    def th_loglike(self, space, inputs, outputs, vector, params, prior=False, noise=False):
-        values, _ = self._values(params)
+    # ---- log-density (WarpedStudentTDistribution.logp_cho, studentT.py:114-146) with nu = th_freedom(prior=True) (:31)
+    def _density(self, logdet, quad, det_m, N, nu):
         t = self.dtype.type
-        c = self._factor(values, inputs, outputs)
-        if not np.all(np.isfinite(c['delta'])) or not np.all(np.isfinite(c['det_m'])):   # cond1, cond2
-            return t(SENTINEL)
-        st = self._solve(c, values, 'logp')
-        if not np.isfinite(st['logdet']) or st['nonfinite'] > 0:                         # cond3, cond4
-            return t(SENTINEL)
-        nu = t(self.f_degree(values))                    # th_freedom(prior=True), studentT.py:31
-        n, beta = t(c['N']), t(st['quad'])
-        with np.errstate(all='ignore'):
-            r1 = t(-0.5) * (nu + n) * np.log1p(beta / (nu - t(2)))                       # :124
-            if t(np.float32(1e6)) <= nu:                                                 # :125
-                r2 = -n * t(0.5) * np.log(t(2.0 * np.float32(np.pi)))
-            else:
-                r2 = t(gammaln((nu + n) * 0.5) - gammaln(nu * 0.5)) - t(0.5) * n * np.log((nu - t(2)) * t(np.float32(np.pi)))
-            return t(r1 + r2 - t(st['logdet']) + c['det_m'])                             # :127-135
+        one = np.ndim(quad) == 0
+        cast = t if one else (lambda v: np.asarray(v, dtype=self.dtype))
+        nu, beta, n = cast(nu), cast(quad), t(N)
+        r1 = t(-0.5) * (nu + n) * np.log1p(beta / (nu - t(2)))                           # :124
+        gauss = lambda: -n * t(0.5) * np.log(t(2.0 * np.float32(np.pi)))                 # :125
+        student = lambda: cast(gammaln((nu + n) * 0.5) - gammaln(nu * 0.5)) - t(0.5) * n * np.log((nu - t(2)) * t(np.float32(np.pi)))
+        big = t(np.float32(1e6)) <= nu
+        if one:          # one row takes its side of the switch alone (np.where evaluates both: two gammaln and a select)
+            r2 = gauss() if big else student()
+        else:
+            r2 = np.where(big, gauss(), student())
+        return r1 + r2 - cast(logdet) + det_m                                            # :127-135
 
     # ---- gradient of logp: the Gaussian chain rule with d logp / d beta = -s/2, s = (nu + n) / (nu - 2 + beta),
     #      plus the degrees-of-freedom term (what Theano's reverse mode gives for studentT.py:114-135)
-    th_dlogp = GaussianProcess.th_dlogp
-    _dloglike = GaussianProcess._dloglike
-    _chain_rule = GaussianProcess._chain_rule
-    _flat_gradient = GaussianProcess._flat_gradient
-    _potential_gradient = GaussianProcess._potential_gradient
-
-    def _dlogp_scale(self, values, c, st, nat):
-        nu, n, beta = float(self.f_degree(values)), float(c['N']), float(st['quad'])
-        deg = self.f_degree.degree
-        if isinstance(deg, HyperVar) and deg.name in nat:
-            g = -0.5 * np.log1p(beta / (nu - 2.0)) + 0.5 * (nu + n) * beta / ((nu - 2.0) * (nu - 2.0 + beta))
-            if not float(np.float32(1e6)) <= nu:
-                g += 0.5 * digamma((nu + n) * 0.5) - 0.5 * digamma(nu * 0.5) - 0.5 * n / (nu - 2.0)
-            nat[deg.name] = nat[deg.name] + g
-        return (nu + n) / (nu - 2.0 + beta)
-
-    # ---- chains of hyper-parameter vectors: the Gaussian block path with the Student-t density and scale per row
-    logp_chain = GaussianProcess.logp_chain
-    dlogp_chain = GaussianProcess.dlogp_chain
-    _chain_workspace = GaussianProcess._chain_workspace
-    _chain_setup = GaussianProcess._chain_setup
-    _chain_members = GaussianProcess._chain_members
-    _chain_delta_or_bad = GaussianProcess._chain_delta_or_bad
-    _chain_factor_block = GaussianProcess._chain_factor_block
-    _potential_gradient_rows = GaussianProcess._potential_gradient_rows
-    _chain_rule_rows = GaussianProcess._chain_rule_rows
-    _flat_gradient_rows = GaussianProcess._flat_gradient_rows
-
-    def _chain_density(self, values_b, st, det_m, N, B):
-        """th_loglike above for B rows: st = [logdet, quad, ...] per row"""
-        t = self.dtype.type
-        nu = self.f_degree.rows(values_b, B).astype(self.dtype)
-        n, beta = t(N), st[:, 1].astype(self.dtype)
-        r1 = t(-0.5) * (nu + n) * np.log1p(beta / (nu - t(2)))                           # :124
-        gauss = -n * t(0.5) * np.log(t(2.0 * np.float32(np.pi)))                         # :125
-        r2 = ((gammaln((nu + n) * 0.5) - gammaln(nu * 0.5)).astype(self.dtype)
-              - t(0.5) * n * np.log((nu - t(2)) * t(np.float32(np.pi))))
-        r2 = np.where(t(np.float32(1e6)) <= nu, gauss, r2)
-        return (r1 + r2 - st[:, 0].astype(self.dtype) + det_m).astype(self.dtype)       # :127-135
-
-    def _chain_dlogp_scale(self, values_b, st, N, nat, ok, B):
-        """_dlogp_scale above for B rows"""
-        nu, n, beta = self.f_degree.rows(values_b, B), float(N), st[:, 1].astype(np.float64)
+    def _dlogp_scale(self, nu, quad, N, nat, ok=None):
+        n = float(N)
+        if np.ndim(quad) == 0:       # one row: the same arithmetic on Python floats (a NumPy scalar costs 10x per operation)
+            nu, beta = float(nu), float(quad)
+        else:
+            nu, beta = np.asarray(nu, dtype=np.float64), np.asarray(quad, dtype=np.float64)
         deg = self.f_degree.degree
         with np.errstate(all='ignore'):
             if isinstance(deg, HyperVar) and deg.name in nat:
                 g = -0.5 * np.log1p(beta / (nu - 2.0)) + 0.5 * (nu + n) * beta / ((nu - 2.0) * (nu - 2.0 + beta))
                 g = g + np.where(float(np.float32(1e6)) <= nu, 0.0,
                                  0.5 * digamma((nu + n) * 0.5) - 0.5 * digamma(nu * 0.5) - 0.5 * n / (nu - 2.0))
-                nat[deg.name] = nat[deg.name] + np.where(ok, g, 0.0).reshape(nat[deg.name].shape)
+                nat[deg.name] = nat[deg.name] + np.reshape(g if ok is None else np.where(ok, g, 0.0), np.shape(nat[deg.name]))
             return (nu + n) / (nu - 2.0 + beta)
 
     # ---- posterior scaling (studentT.py:36-49)
@@ -157,12 +116,7 @@ class WarpedStudentTProcess(StudentTProcess):
 
     def gauss_hermite(self, f, mu, sigma, n=10):
         """studentT.py:99-102"""
-        t = self.dtype.type
-        _a, _w = np.polynomial.hermite.hermgauss(n)
-        a = _a.astype(self.dtype)[:, None]
-        w = _w.astype(self.dtype)
-        grille = mu + sigma * t(np.sqrt(2)) * a
-        return np.dot(w, f(grille.flatten()).reshape(grille.shape)) / t(np.sqrt(np.pi))
+        return gauss_hermite(f, mu, sigma, n, self.dtype)
 
     def th_mean(self, space, inputs, outputs, vector, params, prior=False, noise=False, n=10):
         loc, sd, values = self._loc_sd(space, inputs, outputs, params, prior, noise)

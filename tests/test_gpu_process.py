@@ -899,3 +899,28 @@ def test_student_t_chains_use_the_block_path_and_equal_row_by_row(warped):
     ref = np.array([tp.dlogp(c, array=True) for c in chain])
     np.testing.assert_allclose(tp.dlogp_chain(chain, batch=4), ref, rtol=1e-8, atol=1e-8)
     assert type(tp).dlogp_chain is g3.GaussianProcess.dlogp_chain
+
+
+@pytest.mark.parametrize('warp', ['ArcsinhLinear', 'LogShifted'])
+def test_chains_of_the_arcsinh_and_log_warps_equal_row_by_row(warp):
+    """logp_chain / dlogp_chain of the two warps whose row forms were a Python loop over the rows until every mapping
+    formula broadcast over a block's rows: against one logp / dlogp per row, two blocks (4 + 3 rows); one row of the
+    LogShifted chain has shift > min(y) (the log of a negative number: the -1e30 branch, no likelihood gradient)"""
+    import g3py_amd as g3
+    rng = np.random.default_rng(67)
+    N, d = 96, 2
+    X = rng.uniform(0, 4, (N, d))
+    y = np.exp(0.3 * np.sin(X.sum(1))) + 0.03 * rng.standard_normal(N) + 1.0
+    gp = g3.WGP(space=X[:4], location=g3.Bias(X), kernel=g3.SE(X), mapping=getattr(g3, warp)(y))
+    gp.observed(X, y)
+    base = gp.active.dict_to_array(gp.params)
+    chain = base[None, :] + 0.1 * rng.standard_normal((7, len(base)))
+    if warp == 'LogShifted':
+        keys = [v.key for v in gp.model.vars]
+        chain[3, sum(v.size for v in gp.model.vars[:keys.index('WGP_LogShifted_shift')])] = y.min() + 0.5
+    want = np.array([gp.logp(c, array=True) for c in chain])
+    ref = np.array([gp.dlogp(c, array=True) for c in chain])
+    sentinel = want < -1e29
+    assert sentinel.sum() == (warp == 'LogShifted') and np.all(ref[sentinel] == 0) and np.all(np.abs(ref[~sentinel]).max(axis=1) > 0)
+    np.testing.assert_allclose(gp.logp_chain(chain, batch=4), want, rtol=1e-10)
+    np.testing.assert_allclose(gp.dlogp_chain(chain, batch=4), ref, rtol=1e-8, atol=1e-8)
