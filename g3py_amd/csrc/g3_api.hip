@@ -394,12 +394,7 @@ diag_stats_kernel(T* A, int64_t n, int64_t ld, double* out, int lift, int64_t bs
   if (lane == 0) { s_min[wave] = mn; s_max[wave] = mx; s_sum[wave] = sm; }
   __syncthreads();
   if (tid == 0) {
-    double a = s_min[0], b = s_max[0], c = 0.0;
-    for (int w = 0; w < 16; ++w) {
-      a = (s_min[w] < a || s_min[w] != s_min[w]) ? s_min[w] : a;
-      b = (s_max[w] > b || s_max[w] != s_max[w]) ? s_max[w] : b;
-      c += s_sum[w];
-    }
+    const double a = waves_min<16>(s_min), b = waves_max<16>(s_max), c = waves_sum<16>(s_sum);
     if (out) { out[0] = a; out[1] = c / (double)n; out[2] = b; }
     s_m = a;
   }
@@ -437,27 +432,16 @@ logp_terms_kernel(const T* L, int64_t n, int64_t ld, const T* a, double* out, in
   L += (int64_t)blockIdx.x * bstride;            // batch member (grid.x)
   if (a) a += (int64_t)blockIdx.x * astride;
   out += 4 * blockIdx.x;
-  __shared__ double s0[16], s1[16], s2[16], s3[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double ld_sum = 0, ss = 0, nf = 0, bd = 0;
+  __shared__ double red[4][16];
+  const int tid = threadIdx.x;
+  LogpTerms t;
   for (int64_t i = tid; i < n; i += 1024) {
-    const double d = (double)L[i * ld + i];
-    ld_sum += log(d);
-    if (!(d > 0.0) || __builtin_isinf(d)) bd += 1;
-    if (a) {
-      const double v = (double)a[i];
-      ss += v * v;
-      if (v != v || __builtin_isinf(v)) nf += 1;
-    }
+    t.diag((double)L[i * ld + i]);
+    if (a) t.rhs((double)a[i]);
   }
-  ld_sum = wave_sum(ld_sum); ss = wave_sum(ss); nf = wave_sum(nf); bd = wave_sum(bd);
-  if (lane == 0) { s0[wave] = ld_sum; s1[wave] = ss; s2[wave] = nf; s3[wave] = bd; }
-  __syncthreads();
-  if (tid == 0) {
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    for (int w = 0; w < 16; ++w) { a0 += s0[w]; a1 += s1[w]; a2 += s2[w]; a3 += s3[w]; }
-    out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3;
-  }
+  t.to_waves<16>(red, tid & 63, tid >> 6);
+  if (tid == 0)
+    for (int k = 0; k < 4; ++k) out[k] = waves_sum<16>(red[k]);
 }
 
 // The tail of one evaluation in ONE launch (small problems are bound by the number of launches, ~5 us each):
@@ -467,28 +451,20 @@ template <typename T>
 __global__ void __launch_bounds__(1024)
 logp_finish_kernel(const T* L, int64_t n, int64_t npad, int64_t ld, const T* __restrict__ a_src, T* __restrict__ a_dst,
                    double* out, int* info) {
-  __shared__ double s0[16], s1[16], s2[16], s3[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double ld_sum = 0, ss = 0, nf = 0, bd = 0;
+  __shared__ double red[4][16];
+  const int tid = threadIdx.x;
+  LogpTerms t;
   for (int64_t i = tid; i < npad; i += 1024) {
     const T av = a_src[i];
     a_dst[i] = av;
     if (i < n) {
-      const double d = (double)L[i * ld + i];
-      ld_sum += log(d);
-      if (!(d > 0.0) || __builtin_isinf(d)) bd += 1;
-      const double v = (double)av;
-      ss += v * v;
-      if (v != v || __builtin_isinf(v)) nf += 1;
+      t.diag((double)L[i * ld + i]);
+      t.rhs((double)av);
     }
   }
-  ld_sum = wave_sum(ld_sum); ss = wave_sum(ss); nf = wave_sum(nf); bd = wave_sum(bd);
-  if (lane == 0) { s0[wave] = ld_sum; s1[wave] = ss; s2[wave] = nf; s3[wave] = bd; }
-  __syncthreads();
+  t.to_waves<16>(red, tid & 63, tid >> 6);
   if (tid == 0) {
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    for (int w = 0; w < 16; ++w) { a0 += s0[w]; a1 += s1[w]; a2 += s2[w]; a3 += s3[w]; }
-    out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3;
+    for (int k = 0; k < 4; ++k) out[k] = waves_sum<16>(red[k]);
     out[4] = (double)*info;
     *info = 0;
   }
@@ -533,24 +509,21 @@ rows_dot_ss_kernel(const T* __restrict__ V, int64_t n, int64_t ld, const T* __re
   }
 }
 
-static int fetch_stats(g3_ctx* ctx, double* out, int cnt) {
-  G3_HIP(hipMemcpyAsync(ctx->h_stats, ctx->d_stats, cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+// cnt doubles of the context's reduction scratch, from `off` on, to the host (synchronises the context's stream)
+static int fetch_stats(g3_ctx* ctx, double* out, int cnt, int off = 0) {
+  G3_HIP(hipMemcpyAsync(ctx->h_stats + off, ctx->d_stats + off, cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   G3_HIP(hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < cnt; ++i) out[i] = ctx->h_stats[i];
+  for (int i = 0; i < cnt; ++i) out[i] = ctx->h_stats[off + i];
   return G3_OK;
 }
 
-// one workgroup per member, members `stride` elements apart; the caller checks the launch
-static void diag_stats_members(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double* dout, int lift, int members,
-                               int64_t stride) {
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((diag_stats_kernel<double>), dim3(members), dim3(1024), 0, ctx->stream, (double*)A, n, ld, dout, lift, stride);
-  else
-    hipLaunchKernelGGL((diag_stats_kernel<float>), dim3(members), dim3(1024), 0, ctx->stream, (float*)A, n, ld, dout, lift, stride);
-}
-
-static int diag_stats_launch(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double* dout, int lift) {
-  diag_stats_members(ctx, A, n, ld, dt, dout, lift, 1, 0);
+// one workgroup per member, members `stride` elements apart (one problem: 1 member, stride 0)
+static int diag_stats_launch(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double* dout, int lift, int members = 1,
+                             int64_t stride = 0) {
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((diag_stats_kernel<T>), dim3(members), dim3(1024), 0, ctx->stream, (T*)A, n, ld, dout, lift, stride);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -574,10 +547,7 @@ extern "C" int g3_diag_stats(g3_ctx* ctx, const void* A, int64_t n, int64_t ld, 
   if (!out) return -6;
   int rc = diag_stats_launch(ctx, const_cast<void*>(A), n, ld, dt, ctx->d_stats + 8, 0);
   if (rc) return rc;
-  G3_HIP(hipMemcpyAsync(ctx->h_stats + 8, ctx->d_stats + 8, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  G3_HIP(hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < 3; ++i) out[i] = ctx->h_stats[8 + i];
-  return G3_OK;
+  return fetch_stats(ctx, out, 3, 8);
 }
 
 int g3i_diag_stats_dev(g3_ctx* ctx, const void* A, int64_t n, int64_t ld, g3_dtype dt, double* out_dev) {
@@ -603,8 +573,10 @@ __global__ void scale_kernel(T* A, int64_t rows, int64_t cols, int64_t ld, T f) 
 int g3i_scale(g3_ctx* ctx, void* A, int64_t rows, int64_t cols, int64_t ld, g3_dtype dt, double factor) {
   if (rows <= 0 || cols <= 0) return G3_OK;
   const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)rows);
-  if (dt == G3_F64) hipLaunchKernelGGL((scale_kernel<double>), grid, dim3(256), 0, ctx->stream, (double*)A, rows, cols, ld, factor);
-  else hipLaunchKernelGGL((scale_kernel<float>), grid, dim3(256), 0, ctx->stream, (float*)A, rows, cols, ld, (float)factor);
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((scale_kernel<T>), grid, dim3(256), 0, ctx->stream, (T*)A, rows, cols, ld, (T)factor);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -612,12 +584,10 @@ int g3i_scale(g3_ctx* ctx, void* A, int64_t rows, int64_t cols, int64_t ld, g3_d
 // stream-ordered; in batch mode every member gets the same increment
 int g3i_diag_add(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, double value) {
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)g3_nbatch(ctx));
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((diag_add_kernel<double>), grid, dim3(256), 0, ctx->stream, (double*)A, n, ld, value,
-                       g3_bstride_of(ctx, A));
-  else
-    hipLaunchKernelGGL((diag_add_kernel<float>), grid, dim3(256), 0, ctx->stream, (float*)A, n, ld, (float)value,
-                       g3_bstride_of(ctx, A));
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((diag_add_kernel<T>), grid, dim3(256), 0, ctx->stream, (T*)A, n, ld, (T)value, g3_bstride_of(ctx, A));
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -631,21 +601,22 @@ extern "C" int g3_scrub(g3_ctx* ctx, void* A, int64_t n1, int64_t n2, int64_t ld
   if (ld < n2) return -5;
   if (n1 == 0 || n2 == 0) return G3_OK;
   const dim3 grid((unsigned)((n2 + 255) / 256 > 64 ? 64 : (n2 + 255) / 256), (unsigned)n1);
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((scrub_kernel<double>), grid, dim3(256), 0, ctx->stream, (double*)A, n2, ld);
-  else
-    hipLaunchKernelGGL((scrub_kernel<float>), grid, dim3(256), 0, ctx->stream, (float*)A, n2, ld);
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((scrub_kernel<T>), grid, dim3(256), 0, ctx->stream, (T*)A, n2, ld);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
 
-int g3i_logp_terms_dev(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, const void* a, g3_dtype dt, double* out_dev) {
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((logp_terms_kernel<double>), dim3(1), dim3(1024), 0, ctx->stream, (const double*)L, n, ld,
-                       (const double*)a, out_dev, (int64_t)0, (int64_t)0);
-  else
-    hipLaunchKernelGGL((logp_terms_kernel<float>), dim3(1), dim3(1024), 0, ctx->stream, (const float*)L, n, ld,
-                       (const float*)a, out_dev, (int64_t)0, (int64_t)0);
+// one workgroup per member: factors `lstride`, vectors a `astride` elements apart, four doubles each into out_dev
+int g3i_logp_terms_dev(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, const void* a, g3_dtype dt, double* out_dev, int batch,
+                       int64_t lstride, int64_t astride) {
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((logp_terms_kernel<T>), dim3(batch), dim3(1024), 0, ctx->stream, (const T*)L, n, ld, (const T*)a, out_dev,
+                       lstride, astride);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -694,22 +665,15 @@ static int rows_dot_ss_launch(g3_ctx* ctx, const void* V, int64_t m, int64_t n, 
                               g3_dtype dt, void* dot, void* ss, int batch = 1, int64_t vstride = 0, int64_t astride = 0,
                               int64_t ostride = 0, int64_t tri = 0) {
   if (m == 0) return G3_OK;
-  if (batch > 1 && m <= 1024 && tri == 0) {
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((rows_dot_ss_member_kernel<double>), dim3((unsigned)batch), dim3(256), 0, ctx->stream,
-                         (const double*)V, m, n, ld, (const double*)a, (double*)dot, (double*)ss, vstride, astride, ostride);
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    if (batch > 1 && m <= 1024 && tri == 0)
+      hipLaunchKernelGGL((rows_dot_ss_member_kernel<T>), dim3((unsigned)batch), dim3(256), 0, ctx->stream, (const T*)V, m, n, ld,
+                         (const T*)a, (T*)dot, (T*)ss, vstride, astride, ostride);
     else
-      hipLaunchKernelGGL((rows_dot_ss_member_kernel<float>), dim3((unsigned)batch), dim3(256), 0, ctx->stream,
-                         (const float*)V, m, n, ld, (const float*)a, (float*)dot, (float*)ss, vstride, astride, ostride);
-    G3_LAUNCH_CHECK();
-    return G3_OK;
-  }
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((rows_dot_ss_kernel<double>), dim3((unsigned)m, (unsigned)batch), dim3(256), 0, ctx->stream,
-                       (const double*)V, n, ld, (const double*)a, (double*)dot, (double*)ss, vstride, astride, ostride, tri);
-  else
-    hipLaunchKernelGGL((rows_dot_ss_kernel<float>), dim3((unsigned)m, (unsigned)batch), dim3(256), 0, ctx->stream,
-                       (const float*)V, n, ld, (const float*)a, (float*)dot, (float*)ss, vstride, astride, ostride, tri);
+      hipLaunchKernelGGL((rows_dot_ss_kernel<T>), dim3((unsigned)m, (unsigned)batch), dim3(256), 0, ctx->stream, (const T*)V, n, ld,
+                         (const T*)a, (T*)dot, (T*)ss, vstride, astride, ostride, tri);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -747,6 +711,17 @@ __global__ void pad_row_kernel(T* dst, int64_t ld, const T* src, int64_t n, int6
   if (j >= npad) return;
   for (int64_t r = 0; r < rows; ++r) dst[r * ld + j] = (r == 0 && j < n) ? src[j] : T(0);
 }
+// the right-hand-side block [src; 0] per member: blocks `dstride`, vectors src `sstride` elements apart
+static int pad_row_launch(g3_ctx* ctx, void* dst, int64_t ld, const void* src, int64_t n, int64_t npad, int64_t rows, g3_dtype dt,
+                          int batch = 1, int64_t dstride = 0, int64_t sstride = 0) {
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((pad_row_kernel<T>), dim3((unsigned)((npad + 255) / 256), batch), dim3(256), 0, ctx->stream, (T*)dst, ld,
+                       (const T*)src, n, npad, rows, dstride, sstride);
+  });
+  G3_LAUNCH_CHECK();
+  return G3_OK;
+}
 
 // Shared implementation of g3_gp_factor / g3_gp_factor_predict.  K_dev is a tall buffer:
 //   rows [0, Np)            the covariance, then its factor (lower triangle)
@@ -767,14 +742,8 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
   int rc = G3_OK;
   const unsigned gflags = G3_GRAM_LOWER | G3_GRAM_SCRUB | G3_GRAM_PAD_EYE;
   auto build_rhs = [&]() -> int {
-    const unsigned nb = (unsigned)((Np + 255) / 256);
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((pad_row_kernel<double>), dim3(nb), dim3(256), 0, ctx->stream, (double*)rhs, ldk,
-                         (const double*)delta, N, Np, RB, (int64_t)0, (int64_t)0);
-    else
-      hipLaunchKernelGGL((pad_row_kernel<float>), dim3(nb), dim3(256), 0, ctx->stream, (float*)rhs, ldk,
-                         (const float*)delta, N, Np, RB, (int64_t)0, (int64_t)0);
-    G3_LAUNCH_CHECK();
+    const int r0 = pad_row_launch(ctx, rhs, ldk, delta, N, Np, RB, dt);
+    if (r0) return r0;
     if (M > 0) {
       // V = tt_to_num(cov(Xs, X))  (elliptical.py:78-79)
       const int pr = g3i_prof_begin(ctx, G3_TAG_CROSS_GRAM, (double)(N + M) * d * es_d + (double)N * M * es_d);
@@ -805,12 +774,11 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
   double st4[5];
   auto finish = [&]() -> int {
     const int pr = g3i_prof_begin(ctx, G3_TAG_REDUCE, 2.0 * N * M);
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((logp_finish_kernel<double>), dim3(1), dim3(1024), 0, ctx->stream, (const double*)K, N, Np, ldk,
-                         (const double*)rhs, (double*)a, ctx->d_stats, ctx->d_info);
-    else
-      hipLaunchKernelGGL((logp_finish_kernel<float>), dim3(1), dim3(1024), 0, ctx->stream, (const float*)K, N, Np, ldk,
-                         (const float*)rhs, (float*)a, ctx->d_stats, ctx->d_info);
+    g3_by_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((logp_finish_kernel<T>), dim3(1), dim3(1024), 0, ctx->stream, (const T*)K, N, Np, ldk, (const T*)rhs, (T*)a,
+                         ctx->d_stats, ctx->d_info);
+    });
     G3_LAUNCH_CHECK();
     int r = G3_OK;
     if (M > 0 && (mu || ss)) r = rows_dot_ss_launch(ctx, Vp, M, N, ldk, a, dt, mu, ss);
@@ -984,24 +952,15 @@ static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch,
   double* dstats = dm.stats;
   const int64_t wstride = Np * G3_LB;
   // K_b = tt_to_cov(cov(X)) (elliptical.py:70-71), right-hand-side block = [delta_b; 0]
-  const unsigned nb = (unsigned)((Np + 255) / 256);
   char* rhs = (char*)K + (size_t)Np * ldk * es;
   const bool small = Np <= 2 * G3_LB;       // one workgroup per member does the whole evaluation (g3i_small_factor_batched)
   int pr = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)batch * ((double)N * d + 0.5 * (double)N * (N + 1)) * es);
   rc = g3i_gram_batched(ctx, dm.progs, &first, batch, X, N, ldx, d, dt, K, ldk, kstride, Np,
                         G3_GRAM_LOWER | G3_GRAM_SCRUB | G3_GRAM_PAD_EYE);
-  if (rc) return rc;
-  diag_stats_members(ctx, K, N, ldk, dt, nullptr, 1, batch, kstride);
-  if (!small) {
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((pad_row_kernel<double>), dim3(nb, batch), dim3(256), 0, ctx->stream, (double*)rhs, ldk,
-                         (const double*)delta, N, Np, RB, kstride, ldd);
-    else
-      hipLaunchKernelGGL((pad_row_kernel<float>), dim3(nb, batch), dim3(256), 0, ctx->stream, (float*)rhs, ldk,
-                         (const float*)delta, N, Np, RB, kstride, ldd);
-  }
+  if (!rc) rc = diag_stats_launch(ctx, K, N, ldk, dt, nullptr, 1, batch, kstride);
+  if (!rc && !small) rc = pad_row_launch(ctx, rhs, ldk, delta, N, Np, RB, dt, batch, kstride, ldd);
   g3i_prof_end(ctx, pr);
-  G3_LAUNCH_CHECK();
+  if (rc) return rc;
   pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)batch * ((double)N * N * N / 3.0 + (double)N * N));
   if (small) {
     rc = g3i_small_factor_batched(ctx, K, ldk, kstride, invd, wstride, delta, ldd, a, Np, dstats, batch, N, Np, dt);
@@ -1026,13 +985,8 @@ static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch,
     // a_b = first row of the solved right-hand-side block; log det and a^T a per member
     G3_HIP(hipMemcpy2DAsync(a, (size_t)Np * es, rhs, (size_t)kstride * es, (size_t)Np * es, (size_t)batch,
                             hipMemcpyDeviceToDevice, ctx->stream));
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((logp_terms_kernel<double>), dim3(batch), dim3(1024), 0, ctx->stream, (const double*)K, N, ldk,
-                         (const double*)a, dstats, kstride, Np);
-    else
-      hipLaunchKernelGGL((logp_terms_kernel<float>), dim3(batch), dim3(1024), 0, ctx->stream, (const float*)K, N, ldk,
-                         (const float*)a, dstats, kstride, Np);
-    G3_LAUNCH_CHECK();
+    rc = g3i_logp_terms_dev(ctx, K, N, ldk, a, dt, dstats, batch, kstride, Np);
+    if (rc) return rc;
   }
   double* hst = (double*)malloc(sbytes);
   if (!hst) return G3_ERR_NOMEM;
@@ -1394,10 +1348,9 @@ static int gp_draws_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, 
     // P_b = prog_b(Xs, Xs); with the noise kernel tt_to_cov: scrubbed, non-positive diagonal lifted (elliptical.py:70,74)
     int pr = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)nb * ((double)M * d + 0.5 * (double)M * (M + 1)) * es);
     rc = g3i_gram_batched(ctx, dp, &mine, nb, Xs, M, ldxs, d, dt, Cb, Mp, Mp * Mp, Mp, G3_GRAM_LOWER | (lift ? G3_GRAM_SCRUB : 0u));
-    if (!rc && lift) diag_stats_members(ctx, Cb, M, Mp, dt, nullptr, 1, nb, Mp * Mp);
+    if (!rc && lift) rc = diag_stats_launch(ctx, Cb, M, Mp, dt, nullptr, 1, nb, Mp * Mp);
     g3i_prof_end(ctx, pr);
     if (rc) break;
-    if (hipGetLastError() != hipSuccess) { rc = G3_ERR_HIP; break; }
     if (post) {
       // batch mode first: g3i_reset_info then clears the flags of all nb members; V plays the block-inverse region
       g3_batch_scope mode(ctx, nb, Mp * Mp, Mp * Np, V, (size_t)nb * v1);
@@ -1523,9 +1476,8 @@ extern "C" int g3_gp_sample(g3_ctx* ctx, const void* L_dev, int64_t M, int64_t l
   if (!Z_host) return -6;
   if (S <= 0) return -7;
   if (!out_host) return -9;
-  if (dt == G3_F64)
-    return gp_sample_t<double>(ctx, (const double*)L_dev, M, ldl, (const double*)loc_host, (const double*)Z_host, S,
-                               (double*)out_host);
-  return gp_sample_t<float>(ctx, (const float*)L_dev, M, ldl, (const float*)loc_host, (const float*)Z_host, S,
-                            (float*)out_host);
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    return gp_sample_t<T>(ctx, (const T*)L_dev, M, ldl, (const T*)loc_host, (const T*)Z_host, S, (T*)out_host);
+  });
 }

@@ -257,23 +257,17 @@ int g3i_coop_factor_batched(g3_ctx* ctx, void* K, int64_t ld, int64_t kstride, v
   const unsigned grid = 8u * (unsigned)G * (unsigned)((batch + 7) / 8);
   static bool attr_set[G3_MAX_DEVICES][2] = {};
   const int dev_slot = ctx->device & (G3_MAX_DEVICES - 1);
-  if (dt == G3_F64) {
-    constexpr int LDS = (int)sizeof(DiagLds<double>) > 65536 ? (int)sizeof(DiagLds<double>) : 65536;
-    if (!attr_set[dev_slot][0]) {
-      G3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(coop_factor_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      attr_set[dev_slot][0] = true;
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    constexpr int LDS = (int)sizeof(DiagLds<T>) > 65536 ? (int)sizeof(DiagLds<T>) : 65536;
+    bool& set = attr_set[dev_slot][sizeof(T) == 8 ? 0 : 1];
+    if (!set) {
+      G3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(coop_factor_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+      set = true;
     }
-    hipLaunchKernelGGL((coop_factor_kernel<double>), dim3(grid), dim3(512), LDS, ctx->stream, (double*)K, ld, kstride, (double*)W, wstride,
-                       ctx->d_info, ctl, (int)np, G, batch);
-  } else {
-    constexpr int LDS = (int)sizeof(DiagLds<float>) > 65536 ? (int)sizeof(DiagLds<float>) : 65536;
-    if (!attr_set[dev_slot][1]) {
-      G3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(coop_factor_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      attr_set[dev_slot][1] = true;
-    }
-    hipLaunchKernelGGL((coop_factor_kernel<float>), dim3(grid), dim3(512), LDS, ctx->stream, (float*)K, ld, kstride, (float*)W, wstride,
-                       ctx->d_info, ctl, (int)np, G, batch);
-  }
-  G3_LAUNCH_CHECK();
-  return G3_OK;
+    hipLaunchKernelGGL((coop_factor_kernel<T>), dim3(grid), dim3(512), LDS, ctx->stream, (T*)K, ld, kstride, (T*)W, wstride, ctx->d_info,
+                       ctl, (int)np, G, batch);
+    G3_LAUNCH_CHECK();
+    return G3_OK;
+  });
 }

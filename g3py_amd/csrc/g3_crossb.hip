@@ -206,16 +206,13 @@ int g3i_cross_solve_batched(g3_ctx* ctx, void* Ks, int64_t sstride, const void* 
     return G3_ERR_HIP;
   }
   const bool spill = Np > 2 * G3_LB;
-#define G3_CB_LAUNCH(TT, SP)                                                                                                  \
-  return keepv ? cross_solve_launch<TT, SP, true>(ctx, (TT*)Ks, sstride, (const TT*)L, ldl, lstride, (const TT*)W, wstride,   \
-                                                  (const TT*)a, astride, (TT*)mu, (TT*)ss, ostride, Mp, N, Np, batch)         \
-               : cross_solve_launch<TT, SP, false>(ctx, (TT*)Ks, sstride, (const TT*)L, ldl, lstride, (const TT*)W, wstride,  \
-                                                   (const TT*)a, astride, (TT*)mu, (TT*)ss, ostride, Mp, N, Np, batch)
-  if (dt == G3_F64) {
-    if (spill) G3_CB_LAUNCH(double, true);
-    G3_CB_LAUNCH(double, false);
-  }
-  if (spill) G3_CB_LAUNCH(float, true);
-  G3_CB_LAUNCH(float, false);
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+#define G3_CB_LAUNCH(SP, KV)                                                                                                   \
+  cross_solve_launch<T, SP, KV>(ctx, (T*)Ks, sstride, (const T*)L, ldl, lstride, (const T*)W, wstride, (const T*)a, astride, (T*)mu, \
+                                (T*)ss, ostride, Mp, N, Np, batch)
+    if (spill) return keepv ? G3_CB_LAUNCH(true, true) : G3_CB_LAUNCH(true, false);
+    return keepv ? G3_CB_LAUNCH(false, true) : G3_CB_LAUNCH(false, false);
 #undef G3_CB_LAUNCH
+  });
 }

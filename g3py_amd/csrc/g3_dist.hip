@@ -205,11 +205,6 @@ static int set_block_diag(g3_dist* D, int64_t base, int I, double v, bool identi
 static inline double host_at(const g3_dist* D, const void* h, size_t i) {
   return D->dt == G3_F64 ? ((const double*)h)[i] : (double)((const float*)h)[i];
 }
-// f(T()) with T the plan's type: the launches of this file's own kernel templates
-template <typename F>
-static inline void by_dtype(const g3_dist* D, F f) {
-  if (D->dt == G3_F64) f(double()); else f(float());
-}
 
 // all blocks of a panel that other ranks would send, in ONE launch (a hipMemcpy2DAsync per 2 MB block costs ~20 us each:
 // 70 ms per evaluation at nb = 512, which would be the replay's own artefact, not the schedule's)
@@ -1237,7 +1232,7 @@ extern "C" int g3_dist_gp_factor_predict(g3_dist* D, const g3_kernel_prog* prog,
   if (D->M > 0 && ldxs < D->d) return -8;
   if (!out_host) return -9;
   if (D->M > 0 && (!mean_host || !ss_host)) return -10;
-  if (g3i_validate_prog(prog, D->d) || g3i_validate_prog(prog_cross, D->d)) return -2;
+  if (g3h_validate_prog(prog, D->d) || g3h_validate_prog(prog_cross, D->d)) return -2;
   g3_dev_guard _dg(D->ctx);
   ChainScope _cs(D);
   int rc = factor_robust(D, prog, prog_cross, X_dev, ldx, Xs_dev, ldxs, delta_dev);
@@ -1348,7 +1343,7 @@ static int posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_
   for (int c = 0; c < nch; ++c)
     G3D_HIP(hipMemcpy2DAsync(cov + (size_t)c * pad * ldc * es, (size_t)ldc * es, call + (size_t)perm[c] * pad * Mp * es, (size_t)Mp * es,
                              (size_t)Mp * es, pad, hipMemcpyDeviceToDevice, s));
-  by_dtype(D, [&](auto t) {
+  g3_by_dtype(D->dt, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(mirror_lower_kernel<T>, dim3((unsigned)((Mp + 255) / 256), (unsigned)Mp), dim3(256), 0, s, (T*)cov, Mp, ldc);
   });
@@ -1359,7 +1354,7 @@ static int posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_
 extern "C" int g3_dist_posterior_cov(g3_dist* D, const g3_kernel_prog* prog, const void* Xs_dev, int64_t ldxs, void* cov_dev, int64_t ldc) {
   if (!D) return -1;
   if (!D->planned || D->M <= 0) return -1;
-  if (!prog || g3i_validate_prog(prog, D->d)) return -2;
+  if (!prog || g3h_validate_prog(prog, D->d)) return -2;
   if (!Xs_dev) return -3;
   if (ldxs < D->d) return -4;
   if (!cov_dev) return -5;
@@ -1383,7 +1378,7 @@ extern "C" int g3_dist_posterior_draws(g3_dist* D, const g3_kernel_prog* prog_f,
   if (!Z_host) return -6;
   if (S <= 0) return -7;
   if (!out_host) return -8;
-  if (g3i_validate_prog(prog_f, D->d)) return -2;
+  if (g3h_validate_prog(prog_f, D->d)) return -2;
   g3_dev_guard _dg(D->ctx);
   ChainScope _cs(D);
   {
@@ -1433,7 +1428,7 @@ __global__ void __launch_bounds__(256) rows_dot_kernel(const T* __restrict__ A, 
   const int lane = threadIdx.x & 63;
   double acc = 0.0;
   for (int64_t j = lane; j < cols; j += 64) acc = fma((double)A[r * ld + j], (double)v[j], acc);
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  acc = wave_sum(acc);
   if (lane == 0) out[r] = (T)acc;
 }
 
@@ -1459,7 +1454,7 @@ extern "C" int g3_dist_gp_dlogp(g3_dist* D, const g3_kernel_prog* prog, const g3
     if (D) snprintf(D->err, sizeof(D->err), "g3_dist_gp_dlogp: g3_dist_set_grad(1) and g3_dist_gp_factor_predict first");
     return -1;
   }
-  if (!prog || g3i_validate_prog(prog, D->d)) return -2;
+  if (!prog || g3h_validate_prog(prog, D->d)) return -2;
   if (!map || map->nslots < 0 || map->nslots > G3_GRAD_MAXSLOTS) return -3;
   if (!X_dev) return -4;
   if (ldx < D->d) return -5;
@@ -1479,7 +1474,7 @@ extern "C" int g3_dist_gp_dlogp(g3_dist* D, const g3_kernel_prog* prog, const g3
   char* asend = D->asend;
   G3D_HIP(hipMemsetAsync(asend, 0, (size_t)apr * es, sA));
   if (D->rows_inv > 0) {
-    by_dtype(D, [&](auto t) {
+    g3_by_dtype(D->dt, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL(rows_dot_kernel<T>, dim3((unsigned)((D->rows_inv + 3) / 4)), dim3(256), 0, sA, (const T*)Xinv, D->rows_inv, Np, Np,
                          (const T*)D->avec, (T*)asend);

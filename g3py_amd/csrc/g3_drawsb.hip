@@ -12,8 +12,8 @@
 //      * ONE lane reads the pivot flag and publishes it through an LDS word behind a barrier; every wave branches on that
 //        copy.  The wave programs hold workgroup barriers, so the branch must be uniform over the workgroup: a flag read per
 //        lane straight from memory is not guaranteed to be (VERDICT.md on coop_factor_kernel);
-//      * on failure takes the diagonal mean / minimum and the non-finite count of the lower triangle from K_b (combined in
-//        a fixed order: the mean has the bits of g3_diag_stats for these sizes) and walks G3hJitter -- the one definition
+//      * on failure takes the diagonal mean / minimum and the non-finite count of the lower triangle from K_b (combined by
+//        the functions of g3_reduce.h that g3_diag_stats uses) and walks G3hJitter -- the one definition
 //        of the schedule's arithmetic, shared with the host callers -- until an attempt passes or `maxtries` are used up,
 //        then writes the 1e-10 * I fallback;
 //      * leaves tries / fallback / jitter per member in a device array: the batch comes back in one copy.
@@ -124,13 +124,8 @@ __device__ __forceinline__ void robust_program(const T* K, int64_t ldk, int64_t 
         if (lane == 0) { st.red[0][wv] = sm; st.red[1][wv] = mn; st.red[2][wv] = cnt; }
         __syncthreads();
         if (tid == 0) {
-          double a = st.red[1][0], c = 0.0, e = 0.0;
-          for (int k = 0; k < 8; ++k) {                // the order of diag_stats_kernel (g3_api.hip)
-            a = (st.red[1][k] < a || st.red[1][k] != st.red[1][k]) ? st.red[1][k] : a;
-            c += st.red[0][k];
-            e += st.red[2][k];
-          }
-          const double mean = c / (double)n;
+          const double a = waves_min<8>(st.red[1]), e = waves_sum<8>(st.red[2]);
+          const double mean = waves_sum<8>(st.red[0]) / (double)n;
           const G3hJitter first(mean, a);
           st.dK = first.dK;
           st.lift = first.lift;
@@ -205,17 +200,15 @@ int g3i_potrf_robust_batched(g3_ctx* ctx, const void* K, int64_t ldk, int64_t ks
   const unsigned grid = (unsigned)(batch < RB_MAX_WGS ? batch : RB_MAX_WGS);
   G3_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int) * grid, ctx->stream));      // a flag per workgroup; each leaves its own zero again
   ctx->info_clean = false;
-#define G3_RB_LAUNCH(TT, PP)                                                                                                         \
-  hipLaunchKernelGGL((robust_factor_kernel<TT, PP>), dim3(grid), dim3(512), 0, ctx->stream, (const TT*)K, ldk, kstride, (TT*)L, ldl, \
-                     lstride, (TT*)wscr, ctx->d_info, res_dev, batch, (int)n, (int)np, maxtries)
-  if (dt == G3_F64) {
-    if (np == 2 * G3_LB) G3_RB_LAUNCH(double, true);
-    else G3_RB_LAUNCH(double, false);
-  } else {
-    if (np == 2 * G3_LB) G3_RB_LAUNCH(float, true);
-    else G3_RB_LAUNCH(float, false);
-  }
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+#define G3_RB_LAUNCH(PP)                                                                                                          \
+  hipLaunchKernelGGL((robust_factor_kernel<T, PP>), dim3(grid), dim3(512), 0, ctx->stream, (const T*)K, ldk, kstride, (T*)L, ldl, \
+                     lstride, (T*)wscr, ctx->d_info, res_dev, batch, (int)n, (int)np, maxtries)
+    if (np == 2 * G3_LB) G3_RB_LAUNCH(true);
+    else G3_RB_LAUNCH(false);
 #undef G3_RB_LAUNCH
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -318,12 +311,11 @@ draws_kernel(const T* __restrict__ Lp, int64_t ldl, int64_t lstride, const T* __
 int g3i_draws_batched(g3_ctx* ctx, const void* Lp, int64_t ldl, int64_t lstride, const void* loc, const void* mu, int64_t mustride,
                       const void* Z, void* out, int64_t M, int64_t S, int batch, g3_dtype dt) {
   const dim3 grid((unsigned)((M + 3) / 4), (unsigned)batch);
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((draws_kernel<double>), grid, dim3(256), 0, ctx->stream, (const double*)Lp, ldl, lstride, (const double*)loc,
-                       (const double*)mu, mustride, (const double*)Z, (double*)out, (int)M, (int)S);
-  else
-    hipLaunchKernelGGL((draws_kernel<float>), grid, dim3(256), 0, ctx->stream, (const float*)Lp, ldl, lstride, (const float*)loc,
-                       (const float*)mu, mustride, (const float*)Z, (float*)out, (int)M, (int)S);
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((draws_kernel<T>), grid, dim3(256), 0, ctx->stream, (const T*)Lp, ldl, lstride, (const T*)loc, (const T*)mu,
+                       mustride, (const T*)Z, (T*)out, (int)M, (int)S);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }

@@ -194,8 +194,7 @@ static int launch_t(g3_ctx* ctx, void* C, int64_t ldc, const void* A, int64_t ld
 
 static int launch_dt(g3_ctx* ctx, void* C, int64_t ldc, const void* A, int64_t lda, const void* B,
                      int64_t ldb, int64_t k, double alpha, double beta, g3_dtype dt, const GemmShape& sh, int wide) {
-  if (dt == G3_F64) return launch_t<double>(ctx, C, ldc, A, lda, B, ldb, k, alpha, beta, sh, wide);
-  return launch_t<float>(ctx, C, ldc, A, lda, B, ldb, k, alpha, beta, sh, wide);
+  return g3_by_dtype(dt, [&](auto t) { return launch_t<decltype(t)>(ctx, C, ldc, A, lda, B, ldb, k, alpha, beta, sh, wide); });
 }
 
 int g3i_gemm_nt_ex(g3_ctx* ctx, void* C, int64_t ldc, const void* A, int64_t lda, const void* B,
@@ -272,15 +271,13 @@ int g3i_trsm_stripe(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, void* X,
   // move 1.7x fewer bytes per flop.  Measured (same box, twice): N = 32768 205.8 -> 204.5 ms, 24576 93.3 -> 92.7; below
   // m ~ 12000 there are too few stripes to fill the chip and 32 rows win (N = 8192: 7.09 -> 7.40 ms with 64).
   const int64_t wide_min = ctx->tune.trsm_wide_min;
-  if (wide_min > 0 && m >= wide_min && m % 64 == 0 && g3_nbatch(ctx) == 1) {
-    if (dt == G3_F64) return trsm_stripe_t<double, 64>(ctx, (const double*)L, n, ldl, (double*)X, m, ldx, (const double*)W);
-    return trsm_stripe_t<float, 64>(ctx, (const float*)L, n, ldl, (float*)X, m, ldx, (const float*)W);
-  }
-  if (dt == G3_F64)
-    return thin ? trsm_stripe_t<double, 16>(ctx, (const double*)L, n, ldl, (double*)X, m, ldx, (const double*)W)
-                : trsm_stripe_t<double, 32>(ctx, (const double*)L, n, ldl, (double*)X, m, ldx, (const double*)W);
-  return thin ? trsm_stripe_t<float, 16>(ctx, (const float*)L, n, ldl, (float*)X, m, ldx, (const float*)W)
-              : trsm_stripe_t<float, 32>(ctx, (const float*)L, n, ldl, (float*)X, m, ldx, (const float*)W);
+  const bool wide = wide_min > 0 && m >= wide_min && m % 64 == 0 && g3_nbatch(ctx) == 1;
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const T *Lt = (const T*)L, *Wt = (const T*)W;
+    if (wide) return trsm_stripe_t<T, 64>(ctx, Lt, n, ldl, (T*)X, m, ldx, Wt);
+    return thin ? trsm_stripe_t<T, 16>(ctx, Lt, n, ldl, (T*)X, m, ldx, Wt) : trsm_stripe_t<T, 32>(ctx, Lt, n, ldl, (T*)X, m, ldx, Wt);
+  });
 }
 
 // staircase: row segment s (seg_rows[s] rows, stacked) gets its first seg_cols[s] columns

@@ -525,7 +525,7 @@ gram_grad_kernel(const g3_kernel_prog* __restrict__ prog, g3_grad_map map, const
   for (int s = wv; s < width; s += GG_THREADS / 64) {
     double v = 0.0;
     for (int q = 0; q < GG_THREADS / 64; ++q) v += acc_s[s * GG_THREADS + q * 64 + lane];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    v = wave_sum(v);
     if (lane == 0) partial[(size_t)blockIdx.x * width + s] = v;
   }
 }
@@ -740,6 +740,8 @@ gram_grad_se_kernel(SeGradParams<D> se, const T* __restrict__ X, int64_t N, int6
   }
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
+    // wave_sum's order in a loop left to the compiler: unrolled by force, the NS chains of shuffles are all in flight at once
+    // and cost ~30 VGPRs (a wave per SIMD less for most instantiations)
     double v = vals[s];
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     if (lane == 0) red[s * (GG_THREADS / 64) + wv] = v;
@@ -860,17 +862,12 @@ static int gram_grad_se(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, con
   }
   const dim3 grid((unsigned)nblocks, (unsigned)batch);
   int rec = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)batch * (row0 == 0 && row1 == N ? (double)N * (N + 1) / 2 : (double)ntiles * GG_T * GG_T) * g3_esize(dt));
-#define G3_GRAD_FAST(KIND, PKIND)                                                                                   \
-  do {                                                                                                              \
-    if (dt == G3_F64)                                                                                               \
-      hipLaunchKernelGGL((gram_grad_se_kernel<double, D, KIND, PKIND>), grid, dim3(GG_THREADS), 0, ctx->stream, se,  \
-                         (const double*)X, N, ldx, (const double*)G, ldg, (const double*)alpha, partial, row0, row1, \
-                         dsev, gstride, astride);                                                                   \
-    else                                                                                                            \
-      hipLaunchKernelGGL((gram_grad_se_kernel<float, D, KIND, PKIND>), grid, dim3(GG_THREADS), 0, ctx->stream, se,   \
-                         (const float*)X, N, ldx, (const float*)G, ldg, (const float*)alpha, partial, row0, row1,   \
-                         dsev, gstride, astride);                                                                   \
-  } while (0)
+#define G3_GRAD_FAST(KIND, PKIND)                                                                                            \
+  g3_by_dtype(dt, [&](auto t) {                                                                                              \
+    using T = decltype(t);                                                                                                   \
+    hipLaunchKernelGGL((gram_grad_se_kernel<T, D, KIND, PKIND>), grid, dim3(GG_THREADS), 0, ctx->stream, se, (const T*)X, N, \
+                       ldx, (const T*)G, ldg, (const T*)alpha, partial, row0, row1, dsev, gstride, astride);                 \
+  })
   if (lper >= 0) {
     if constexpr (D == 1 || D == 2 || D == 4 || D == 8) {
 #define G3_GRAD_FAST_PK(PKIND)                                  \
@@ -1066,22 +1063,17 @@ int g3i_gram_grad_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, c
     if (rc) return rc;
   }
   const size_t lds = fixed + (size_t)window * GG_THREADS * sizeof(double);
-  if (dt == G3_F64)
-    G3_HIP(hipFuncSetAttribute((const void*)gram_grad_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  else
-    G3_HIP(hipFuncSetAttribute((const void*)gram_grad_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const void* kern = g3_by_dtype(dt, [](auto t) { return (const void*)gram_grad_kernel<decltype(t)>; });
+  G3_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int rec = g3i_prof_begin(ctx, G3_TAG_GRAM, (double)batch * (row0 == 0 && row1 == N ? (double)N * (N + 1) / 2 : (double)ntiles * GG_T * GG_T) * g3_esize(dt));
   const dim3 grid((unsigned)nblocks, (unsigned)batch);
   for (int lo = 0; lo < nslots; lo += window) {
     const int width = nslots - lo < window ? nslots - lo : window;
-    if (dt == G3_F64)
-      hipLaunchKernelGGL((gram_grad_kernel<double>), grid, dim3(GG_THREADS), lds, ctx->stream, dprog, *map,
-                         (const double*)X, N, ldx, d, (const double*)G, ldg, (const double*)alpha, partial, lo, width, row0, row1,
-                         gstride, astride);
-    else
-      hipLaunchKernelGGL((gram_grad_kernel<float>), grid, dim3(GG_THREADS), lds, ctx->stream, dprog, *map,
-                         (const float*)X, N, ldx, d, (const float*)G, ldg, (const float*)alpha, partial, lo, width, row0, row1,
-                         gstride, astride);
+    g3_by_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((gram_grad_kernel<T>), grid, dim3(GG_THREADS), lds, ctx->stream, dprog, *map, (const T*)X, N, ldx, d,
+                         (const T*)G, ldg, (const T*)alpha, partial, lo, width, row0, row1, gstride, astride);
+    });
     G3_LAUNCH_CHECK();
     hipLaunchKernelGGL(grad_reduce_kernel, dim3(width, (unsigned)batch), dim3(256), 0, ctx->stream, partial, nblocks, width, dout + lo, ostride);
     G3_LAUNCH_CHECK();

@@ -287,12 +287,11 @@ __global__ void gram_diag_kernel(const g3_kernel_prog* __restrict__ prog, const 
 int g3i_gram_diag_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, int batch, const void* X, int64_t n, int64_t ldx, int d,
                           g3_dtype dt, void* out, int64_t ostride) {
   const dim3 grid((unsigned)((n + 63) / 64), (unsigned)batch);
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((gram_diag_kernel<double>), grid, dim3(64), 64 * (d | 1) * sizeof(double), ctx->stream, dprogs,
-                       (const double*)X, n, ldx, d, (double*)out, ostride);
-  else
-    hipLaunchKernelGGL((gram_diag_kernel<float>), grid, dim3(64), 64 * (d | 1) * sizeof(float), ctx->stream, dprogs,
-                       (const float*)X, n, ldx, d, (float*)out, ostride);
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((gram_diag_kernel<T>), grid, dim3(64), 64 * (d | 1) * sizeof(T), ctx->stream, dprogs, (const T*)X, n, ldx, d,
+                       (T*)out, ostride);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -313,10 +312,6 @@ int g3i_upload_prog(g3_ctx* ctx, const g3_kernel_prog* prog, int /*slot*/, const
   *dptr = &ctx->d_prog[s];
   return G3_OK;
 }
-
-int g3i_validate_prog(const g3_kernel_prog* p, int d);
-static int validate_prog(const g3_kernel_prog* p, int d) { return g3i_validate_prog(p, d); }
-int g3i_validate_prog(const g3_kernel_prog* p, int d) { return g3h_validate_prog(p, d); }
 
 static dim3 gram_grid(int64_t n1pad, int64_t n2pad, unsigned flags) {
   const int64_t tr = (n1pad + GT - 1) / GT, tc = (n2pad + GTN - 1) / GTN;
@@ -423,19 +418,13 @@ int g3i_gram_rect_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_ke
   ctx->gram_paths[2] += 1;
   int ntrig = prog_trig_pairs(first_host);
   if (ntrig > 16) ntrig = 0;
-  if (dt == G3_F64) {
-    const size_t lds = (GT + GTN) * ((d | 1) + (ntrig ? 2 * ntrig + 1 : 0)) * sizeof(double);
-    SeParams<double, 1> dummy{};
-    hipLaunchKernelGGL((gram_kernel<double, 1, -1, -1>), grid, dim3(256), lds, ctx->stream, dprogs, dummy,
-                       (const double*)X1, n1, ldx1, (const double*)X2, n2, ldx2, d, (double*)K, ldk, n1pad, n2pad, flags, sym,
-                       ntrig, kstride, (int64_t)0);
-  } else {
-    const size_t lds = (GT + GTN) * ((d | 1) + (ntrig ? 2 * ntrig + 1 : 0)) * sizeof(float);
-    SeParams<float, 1> dummy{};
-    hipLaunchKernelGGL((gram_kernel<float, 1, -1, -1>), grid, dim3(256), lds, ctx->stream, dprogs, dummy,
-                       (const float*)X1, n1, ldx1, (const float*)X2, n2, ldx2, d, (float*)K, ldk, n1pad, n2pad, flags, sym,
-                       ntrig, kstride, (int64_t)0);
-  }
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const size_t lds = (GT + GTN) * ((d | 1) + (ntrig ? 2 * ntrig + 1 : 0)) * sizeof(T);
+    SeParams<T, 1> dummy{};
+    hipLaunchKernelGGL((gram_kernel<T, 1, -1, -1>), grid, dim3(256), lds, ctx->stream, dprogs, dummy, (const T*)X1, n1, ldx1,
+                       (const T*)X2, n2, ldx2, d, (T*)K, ldk, n1pad, n2pad, flags, sym, ntrig, kstride, (int64_t)0);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -445,8 +434,6 @@ int g3i_gram_batched(g3_ctx* ctx, const g3_kernel_prog* dprogs, const g3_kernel_
                      int64_t kstride, int64_t npad, unsigned flags) {
   return g3i_gram_rect_batched(ctx, dprogs, first_host, batch, X, n, ldx, X, n, ldx, d, dt, K, ldk, kstride, npad, npad, flags, 1);
 }
-
-int g3i_validate_prog(const g3_kernel_prog* p, int d);
 
 extern "C" int g3_gram(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X1, int64_t n1, int64_t ldx1,
                        const void* X2, int64_t n2, int64_t ldx2, int d, g3_dtype dt, void* K, int64_t ldk,
@@ -462,18 +449,17 @@ extern "C" int g3_gram(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X1, 
   if (d < 1 || d > G3_MAXCOLS) return -9;
   if (ldx1 < d) return -5;
   if (ldx2 < d) return -8;
-  if (validate_prog(prog, d)) return -2;
+  if (g3h_validate_prog(prog, d)) return -2;
   if (!K) return -11;
   if (n1pad < n1) return -13;
   if (n2pad < n2 && !sym) return -14;   // symmetric case: n2pad < n1 limits the columns written
   if (ldk < n2pad) return -12;
   if (!sym && (flags & G3_GRAM_LOWER)) return -15;
   if (n1pad == 0 || n2pad == 0) return G3_OK;
-  if (dt == G3_F64)
-    return gram_t<double>(ctx, prog, (const double*)X1, n1, ldx1, (const double*)X2, n2, ldx2, d, (double*)K,
-                          ldk, n1pad, n2pad, flags, sym);
-  return gram_t<float>(ctx, prog, (const float*)X1, n1, ldx1, (const float*)X2, n2, ldx2, d, (float*)K, ldk,
-                       n1pad, n2pad, flags, sym);
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    return gram_t<T>(ctx, prog, (const T*)X1, n1, ldx1, (const T*)X2, n2, ldx2, d, (T*)K, ldk, n1pad, n2pad, flags, sym);
+  });
 }
 
 // Rows [row0, row0 + nrows) and columns [0, row0 + nrows) of the SQUARE covariance of X (the
@@ -488,7 +474,7 @@ extern "C" int g3_gram_rows(g3_ctx* ctx, const g3_kernel_prog* prog, const void*
   if (N < 0) return -4;
   if (d < 1 || d > G3_MAXCOLS) return -6;
   if (ldx < d) return -5;
-  if (validate_prog(prog, d)) return -2;
+  if (g3h_validate_prog(prog, d)) return -2;
   if (row0 < 0) return -7;
   if (nrows < 0) return -8;
   if (!K) return -10;
@@ -500,13 +486,10 @@ extern "C" int g3_gram_rows(g3_ctx* ctx, const g3_kernel_prog* prog, const void*
   const int64_t n2 = N < row0 + nrows ? N : row0 + nrows;
   const void* X1 = (const char*)X + (size_t)(row0 < N ? row0 : 0) * ldx * es;
   ctx->gram_diag_off = row0;
-  int rc;
-  if (dt == G3_F64)
-    rc = gram_t<double>(ctx, prog, (const double*)X1, n1, ldx, (const double*)X, n2, ldx, d, (double*)K, ldk, nrows,
-                        row0 + nrows, flags, 1);
-  else
-    rc = gram_t<float>(ctx, prog, (const float*)X1, n1, ldx, (const float*)X, n2, ldx, d, (float*)K, ldk, nrows,
-                       row0 + nrows, flags, 1);
+  const int rc = g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    return gram_t<T>(ctx, prog, (const T*)X1, n1, ldx, (const T*)X, n2, ldx, d, (T*)K, ldk, nrows, row0 + nrows, flags, 1);
+  });
   ctx->gram_diag_off = 0;
   return rc;
 }
@@ -520,7 +503,7 @@ extern "C" int g3_gram_diag(g3_ctx* ctx, const g3_kernel_prog* prog, const void*
   if (n < 0) return -4;
   if (d < 1 || d > G3_MAXCOLS) return -6;
   if (ldx < d) return -5;
-  if (validate_prog(prog, d)) return -2;
+  if (g3h_validate_prog(prog, d)) return -2;
   if (!diag) return -8;
   if (n == 0) return G3_OK;
   const g3_kernel_prog* dprog;

@@ -830,7 +830,7 @@ int std_grad_slots(const g3_kernel_prog* p) {
 
 extern "C" int g3_grad_jit_check(const g3_kernel_prog* prog, int d, g3_dtype dt, int64_t* code_bytes, char* log, int64_t log_bytes) {
   if (!prog) return -1;
-  if (g3i_validate_prog(prog, d)) return -2;
+  if (g3h_validate_prog(prog, d)) return -2;
   int ntrig = 0;
   const std::string tables = structure_tables(prog, d, &ntrig);
   std::string code, lg;
@@ -876,7 +876,7 @@ hipFunction_t g3i_grad_jit_function(g3_ctx* ctx, const g3_kernel_prog* prog_host
 // or the compiler's status with its log (tests/test_host.py runs the whole kernel zoo through it on the build host).
 extern "C" int g3_gram_jit_check(const g3_kernel_prog* prog, int d, g3_dtype dt, int64_t* code_bytes, char* log, int64_t log_bytes) {
   if (!prog) return -1;
-  if (g3i_validate_prog(prog, d)) return -2;
+  if (g3h_validate_prog(prog, d)) return -2;
   int ntrig = 0;
   const std::string tables = structure_tables(prog, d, &ntrig);
   std::string code, lg;

@@ -7,6 +7,7 @@
 
 #include "g3hip.h"
 #include "g3_host.h"
+#include "g3_reduce.h"
 
 #define G3_LB 128   // diagonal block factored + inverted by ONE fused kernel; matrices are padded to it
 
@@ -194,30 +195,12 @@ struct g3_sweep_scope {
 static inline size_t g3_esize(g3_dtype dt) { return dt == G3_F64 ? 8 : 4; }
 static inline int64_t g3_roundup(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
 
-// wave reductions in a fixed order (lane 0 holds the result); min / max propagate NaN like numpy
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_min(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    T u = __shfl_down(v, o, 64);
-    v = (u < v || u != u) ? u : v;  // NaN propagates like numpy.min
-  }
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    T u = __shfl_down(v, o, 64);
-    v = (u > v || u != u) ? u : v;
-  }
-  return v;
+// The library's one way from a g3_dtype to a type: f(T()) with T = double for G3_F64, float otherwise; returns what f returns.
+//   return g3_by_dtype(dt, [&](auto t) { using T = decltype(t); return launch_t<T>(...); });
+template <typename F>
+static inline auto g3_by_dtype(g3_dtype dt, F&& f) {
+  if (dt == G3_F64) return f(double());
+  return f(float());
 }
 
 // a context on the caller's stream that creates no stream of its own; the low-priority side stream on first need
@@ -264,7 +247,9 @@ int g3i_read_info(g3_ctx* ctx, int* info_host);
 bool g3i_info_known_zero(const g3_ctx* ctx);
 // g3_diag_stats / g3_logp_terms / g3_rows_dot_ss results left in device memory (no host synchronisation): 3 / 4 doubles
 int g3i_diag_stats_dev(g3_ctx* ctx, const void* A, int64_t n, int64_t ld, g3_dtype dt, double* out_dev);
-int g3i_logp_terms_dev(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, const void* a, g3_dtype dt, double* out_dev);
+// (logp_terms for `batch` members: factors lstride, vectors a astride elements apart, four doubles each)
+int g3i_logp_terms_dev(g3_ctx* ctx, const void* L, int64_t n, int64_t ld, const void* a, g3_dtype dt, double* out_dev, int batch = 1,
+                       int64_t lstride = 0, int64_t astride = 0);
 // batch members of at most 256 padded rows: factor + block inverses + a = L^-1 delta + the four logp scalars, one
 // workgroup per member, one launch (g3_potrf.hip)
 int g3i_small_factor_batched(g3_ctx* ctx, void* K, int64_t ld, int64_t kstride, void* W, int64_t wstride, const void* delta, int64_t ldd,
@@ -317,7 +302,6 @@ int g3i_potrf_robust_batched(g3_ctx* ctx, const void* K, int64_t ldk, int64_t ks
 // out[b] = loc[b] (+ mu[b]) + Lp_b Z[b]: Lp factors lstride apart, loc batch x M, mu batch x mustride or null, Z / out batch x M x S
 int g3i_draws_batched(g3_ctx* ctx, const void* Lp, int64_t ldl, int64_t lstride, const void* loc, const void* mu, int64_t mustride,
                       const void* Z, void* out, int64_t M, int64_t S, int batch, g3_dtype dt);
-int g3i_validate_prog(const g3_kernel_prog* p, int d);
 // the Gram kernel generated for prog's structure (g3_gram_jit.hip); 0 = launched, 1 = none (the caller interprets)
 int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_prog* prog_dev, int batch, const void* X1, int64_t n1,
                  int64_t ldx1, const void* X2, int64_t n2, int64_t ldx2, int d, g3_dtype dt, void* K, int64_t ldk, int64_t n1pad,
@@ -331,9 +315,9 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
 // the fields' offsets cannot touch structure).  0 and *first = member 0, the structure all share; 1 = refuse (status -2).
 static inline int g3i_validate_members(const MemberProgs& mp, int batch, int d, g3_kernel_prog* first) {
   mp.member(0, first);
-  if (!mp.progs) return g3i_validate_prog(mp.tmpl, d) || g3i_validate_prog(first, d);
+  if (!mp.progs) return g3h_validate_prog(mp.tmpl, d) || g3h_validate_prog(first, d);
   for (int b = 0; b < batch; ++b)
-    if (g3i_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return 1;
+    if (g3h_validate_prog(&mp.progs[b], d) || !g3h_same_structure(&mp.progs[0], &mp.progs[b])) return 1;
   return 0;
 }
 

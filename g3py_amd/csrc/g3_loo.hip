@@ -215,11 +215,11 @@ extern "C" int g3_gp_loo_batched(g3_ctx* ctx, int batch, const void* L_dev, int6
   const int64_t wstride = Np * G3_LB;
   if (Np <= 2 * G3_LB) {
     const int rec = g3i_prof_begin(ctx, G3_TAG_TRSM, (double)batch * (double)N * N * N / 3.0);
-    const int rc = dt == G3_F64
-        ? loo_small_launch<double>(ctx, (const double*)L_dev, ldl, kstride, (const double*)invd_dev, wstride, (const double*)a_dev,
-                                   Np, (double*)alpha_dev, (double*)kdiag_dev, Np, N, Np, batch)
-        : loo_small_launch<float>(ctx, (const float*)L_dev, ldl, kstride, (const float*)invd_dev, wstride, (const float*)a_dev, Np,
-                                  (float*)alpha_dev, (float*)kdiag_dev, Np, N, Np, batch);
+    const int rc = g3_by_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      return loo_small_launch<T>(ctx, (const T*)L_dev, ldl, kstride, (const T*)invd_dev, wstride, (const T*)a_dev, Np, (T*)alpha_dev,
+                                 (T*)kdiag_dev, Np, N, Np, batch);
+    });
     g3i_prof_end(ctx, rec);
     return rc;
   }

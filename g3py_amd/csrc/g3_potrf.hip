@@ -134,33 +134,18 @@ small_factor_kernel(T* K, int64_t ld, int64_t kstride, T* Wall, int64_t wstride,
     if (tid < G3_LB) vec[G3_LB + tid] = a1;
     __syncthreads();
   }
-  // a and the four scalars of logp_terms_kernel (g3_api.hip): sum log L_ii, a^T a, #non-finite a, #bad diagonal
-  double ld_sum = 0, ss = 0, nf = 0, bd = 0;
+  // a and the four scalars of the evaluation, one per thread at the end
+  LogpTerms t;
   for (int i = tid; i < np; i += 512) {
     const T v = vec[i];
     a_out[(int64_t)b * astride + i] = v;
     if (i < n) {
-      const double dg = (double)A[(int64_t)i * ld + i];
-      ld_sum += log(dg);
-      if (!(dg > 0.0) || __builtin_isinf(dg)) bd += 1;
-      const double dv = (double)v;
-      ss += dv * dv;
-      if (dv != dv || __builtin_isinf(dv)) nf += 1;
+      t.diag((double)A[(int64_t)i * ld + i]);
+      t.rhs((double)v);
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    ld_sum += __shfl_down(ld_sum, off);
-    ss += __shfl_down(ss, off);
-    nf += __shfl_down(nf, off);
-    bd += __shfl_down(bd, off);
-  }
-  if (lane == 0) { red[0][wv] = ld_sum; red[1][wv] = ss; red[2][wv] = nf; red[3][wv] = bd; }
-  __syncthreads();
-  if (tid < 4) {
-    double t = 0;
-    for (int k = 0; k < 8; ++k) t += red[tid][k];
-    stats[4 * b + tid] = t;
-  }
+  t.to_waves<8>(red, lane, wv);
+  if (tid < 4) stats[4 * b + tid] = waves_sum<8>(red[tid]);
 }
 
 // the fused small-N evaluation of a batch (np = 128 or 256 padded rows per member); the members' covariances are in K
@@ -169,12 +154,11 @@ int g3i_small_factor_batched(g3_ctx* ctx, void* K, int64_t ld, int64_t kstride, 
   if (np != G3_LB && np != 2 * G3_LB) return -1;
   G3_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int) * batch, ctx->stream));
   ctx->info_clean = false;
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((small_factor_kernel<double>), dim3((unsigned)batch), dim3(512), 0, ctx->stream, (double*)K, ld, kstride, (double*)W,
-                       wstride, (const double*)delta, ldd, (double*)a, astride, dstats, ctx->d_info, (int)n, (int)np);
-  else
-    hipLaunchKernelGGL((small_factor_kernel<float>), dim3((unsigned)batch), dim3(512), 0, ctx->stream, (float*)K, ld, kstride, (float*)W,
-                       wstride, (const float*)delta, ldd, (float*)a, astride, dstats, ctx->d_info, (int)n, (int)np);
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((small_factor_kernel<T>), dim3((unsigned)batch), dim3(512), 0, ctx->stream, (T*)K, ld, kstride, (T*)W, wstride,
+                       (const T*)delta, ldd, (T*)a, astride, dstats, ctx->d_info, (int)n, (int)np);
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -448,13 +432,15 @@ int g3i_potrf_tall(g3_ctx* ctx, void* A, int64_t n, int64_t ld, g3_dtype dt, voi
 
   int G = 1;
   int64_t NB = g3i_panel_width(ctx, n, &G);
-  if (n >= 3 * NB) {
-    if (dt == G3_F64) return potrf_lookahead<double>(ctx, (double*)A, n, ld, (double*)invd, NB, G, dt, E);
-    return potrf_lookahead<float>(ctx, (float*)A, n, ld, (float*)invd, NB, G, dt, E);
-  }
-  int rc;
-  if (dt == G3_F64) rc = potrf_rec<double>(ctx, (double*)A, n, ld, (double*)invd, 0, dt);
-  else rc = potrf_rec<float>(ctx, (float*)A, n, ld, (float*)invd, 0, dt);
+  if (n >= 3 * NB)
+    return g3_by_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      return potrf_lookahead<T>(ctx, (T*)A, n, ld, (T*)invd, NB, G, dt, E);
+    });
+  const int rc = g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    return potrf_rec<T>(ctx, (T*)A, n, ld, (T*)invd, 0, dt);
+  });
   if (rc || E == 0) return rc;
   return g3i_trsm_rlt(ctx, A, n, ld, (char*)A + (size_t)n * ld * g3_esize(dt), E, ld, dt, invd);
 }
@@ -517,13 +503,12 @@ int g3i_trsm_rlt(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, void* B, in
   // few rows against a long factor, outside batch mode and not from inside a two-stream sweep: that sweep owns the side
   // stream and the event pool.  Default panels are at most 1024 wide, so a sweep never asks for n >= 4096; with G3_NB >= 4096
   // a panel solve of g3i_potri does, and takes the one-stream recursion below instead of a sweep nested in its own
-  if (n >= 4096 && m <= 4096 && ctx->batch <= 1 && !ctx->in_sweep) {
-    if (dt == G3_F64) return trsm_lookahead<double>(ctx, (const double*)L, n, ldl, (double*)B, m, ldb, (const double*)invd, dt);
-    return trsm_lookahead<float>(ctx, (const float*)L, n, ldl, (float*)B, m, ldb, (const float*)invd, dt);
-  }
-  if (dt == G3_F64)
-    return trsm_rec<double>(ctx, (const double*)L, n, ldl, (double*)B, m, ldb, (const double*)invd, dt);
-  return trsm_rec<float>(ctx, (const float*)L, n, ldl, (float*)B, m, ldb, (const float*)invd, dt);
+  const bool sweep = n >= 4096 && m <= 4096 && ctx->batch <= 1 && !ctx->in_sweep;
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    if (sweep) return trsm_lookahead<T>(ctx, (const T*)L, n, ldl, (T*)B, m, ldb, (const T*)invd, dt);
+    return trsm_rec<T>(ctx, (const T*)L, n, ldl, (T*)B, m, ldb, (const T*)invd, dt);
+  });
 }
 
 int g3i_trtri_blocks(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, g3_dtype dt, void* invd) {
@@ -531,14 +516,12 @@ int g3i_trtri_blocks(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, g3_dtyp
   ctx->info_clean = false;       // the inversion kernel takes the flag read-write
 
   const unsigned nb = (unsigned)(n / LB);
-  if (dt == G3_F64)
-    hipLaunchKernelGGL((diag128m_kernel<double, false>), dim3(nb, (unsigned)g3_nbatch(ctx)), dim3(512), 0, ctx->stream,
-                       (double*)const_cast<void*>(L), ldl, LB * (ldl + 1), (double*)invd, LB, LB * LB,
-                       ctx->d_info, (int64_t)0, g3_bstride_of(ctx, L), g3_bstride_of(ctx, invd));
-  else
-    hipLaunchKernelGGL((diag128m_kernel<float, false>), dim3(nb, (unsigned)g3_nbatch(ctx)), dim3(512), 0, ctx->stream,
-                       (float*)const_cast<void*>(L), ldl, LB * (ldl + 1), (float*)invd, LB, LB * LB,
-                       ctx->d_info, (int64_t)0, g3_bstride_of(ctx, L), g3_bstride_of(ctx, invd));
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((diag128m_kernel<T, false>), dim3(nb, (unsigned)g3_nbatch(ctx)), dim3(512), 0, ctx->stream,
+                       (T*)const_cast<void*>(L), ldl, LB * (ldl + 1), (T*)invd, LB, LB * LB, ctx->d_info, (int64_t)0,
+                       g3_bstride_of(ctx, L), g3_bstride_of(ctx, invd));
+  });
   G3_LAUNCH_CHECK();
   return G3_OK;
 }
@@ -620,8 +603,10 @@ static int trtri_full_t(g3_ctx* ctx, const T* L, int64_t n, const T* W, T* V, T*
 // (d_info of this context, left by the factorisation just before) turns the launches into no-ops.
 int g3i_trtri_full(g3_ctx* ctx, const void* L, int64_t n, const void* W, void* V, void* Vt, void* U, g3_dtype dt) {
   if (n < LB || n > 2048 || (n & (n - 1)) != 0) return -3;
-  if (dt == G3_F64) return trtri_full_t<double>(ctx, (const double*)L, n, (const double*)W, (double*)V, (double*)Vt, (double*)U);
-  return trtri_full_t<float>(ctx, (const float*)L, n, (const float*)W, (float*)V, (float*)Vt, (float*)U);
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    return trtri_full_t<T>(ctx, (const T*)L, n, (const T*)W, (T*)V, (T*)Vt, (T*)U);
+  });
 }
 
 extern "C" int g3_trtri_full(g3_ctx* ctx, const void* L_dev, int64_t n, const void* invd_dev, void* V_dev, void* Vt_dev, void* U_dev,
@@ -707,9 +692,10 @@ extern "C" int g3_potrf_nowait(g3_ctx* ctx, void* A_dev, int64_t n, int64_t ld, 
     // 256-wide kernel) instead of the two-stream sweep tuned for a stand-alone small matrix
     G3_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int) * g3_nbatch(ctx), ctx->stream));
     ctx->info_clean = false;
-    if (n == 0) rc = G3_OK;
-    else if (dt == G3_F64) rc = potrf_rec<double>(ctx, (double*)A_dev, n, ld, (double*)invd_dev, 0, dt);
-    else rc = potrf_rec<float>(ctx, (float*)A_dev, n, ld, (float*)invd_dev, 0, dt);
+    rc = n == 0 ? G3_OK : g3_by_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      return potrf_rec<T>(ctx, (T*)A_dev, n, ld, (T*)invd_dev, 0, dt);
+    });
   } else {
     rc = g3i_potrf(ctx, A_dev, n, ld, dt, invd_dev);
   }
@@ -871,9 +857,8 @@ extern "C" int g3_potrf_robust(g3_ctx* ctx, const void* K_dev, int64_t ldk, void
     if (jitter_host) *jitter_host = 0;
     return G3_OK;
   }
-  if (dt == G3_F64)
-    return robust_t<double>(ctx, (const double*)K_dev, ldk, (double*)L_dev, ldl, n, dt, maxtries,
-                            tries_host, fallback_host, jitter_host);
-  return robust_t<float>(ctx, (const float*)K_dev, ldk, (float*)L_dev, ldl, n, dt, maxtries,
-                         tries_host, fallback_host, jitter_host);
+  return g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    return robust_t<T>(ctx, (const T*)K_dev, ldk, (T*)L_dev, ldl, n, dt, maxtries, tries_host, fallback_host, jitter_host);
+  });
 }
