@@ -1145,6 +1145,58 @@ extern "C" int g3_gram_grad_rows(g3_ctx* ctx, const g3_kernel_prog* prog, const 
   return g3i_gram_grad(ctx, prog, map, X_dev, N, ldx, d, dt, G_rows_dev, ldg, alpha_dev, out_host, row0, nrows);
 }
 
+// ---- pull a covariance adjoint back to the kernel parameters (g3_gram_vjp): what tt.grad through Kernel.cov does with the
+// lower-triangular Kbar that CholeskyRobust.grad returns (g3py/libs/tensors.py:224-260).  The kernels above weight pair (i, j)
+// of the lower triangle with (i == j ? 1/2 : 1) (alpha_i alpha_j - G_ij); with alpha = 0 and G = -Kbar, its diagonal doubled,
+// that weight is Kbar_ij exactly (0 - x and the factor 1/2 * 2 round nothing), so the same launches in the same order give
+// sum_{i >= j} Kbar_ij dK_ij / dparam.  G and the zero alpha live in the context's workspace BEHIND the part the three paths
+// use for their partial sums and outputs: for one member at most 4096 workgroups x 52 slots x 8 B and 4.2 KB, under 2 MiB.
+#define GG_VJP_HEAD ((size_t)4 << 20)
+template <typename T>
+__global__ void __launch_bounds__(256)
+vjp_weight_kernel(T* __restrict__ G, int64_t ldg, const T* __restrict__ Kbar, int64_t ldk, int64_t n) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  for (int64_t i = blockIdx.y; i < n; i += gridDim.y)      // the lower triangle only: nothing above it is read or written
+    if (j <= i) G[i * ldg + j] = (j == i ? T(-2) : T(-1)) * Kbar[i * ldk + j];
+}
+
+extern "C" int g3_gram_vjp(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev, int64_t N,
+                           int64_t ldx, int d, g3_dtype dt, const void* Kbar_dev, int64_t ldk, double* out_host) {
+  if (!ctx) return -1;
+  g3_dev_guard _dg(ctx);
+  if (!prog || prog->nleaf < 0 || prog->nleaf > G3_MAXLEAF || prog->nprod < 0 || prog->nprod > G3_MAXPROD) return -2;
+  if (!map || check_map(prog, map)) return -3;
+  if (!X_dev && N > 0) return -4;
+  if (N < 0) return -5;
+  if (d < 1 || d > G3_MAXCOLS) return -7;
+  if (ldx < d) return -6;
+  if (dt != G3_F64 && dt != G3_F32) return -8;
+  if (!Kbar_dev && N > 0) return -9;
+  if (ldk < N) return -10;
+  if (!out_host) return -11;
+  const size_t es = g3_esize(dt);
+  const size_t gbytes = (size_t)g3_roundup((int64_t)((size_t)N * N * es), 256);
+  if (g3i_ensure_work(ctx, GG_VJP_HEAD + gbytes + (size_t)N * es) != G3_OK) {
+    (void)hipGetLastError();
+    return G3_ERR_NOMEM;
+  }
+  char* G = (char*)ctx->work + GG_VJP_HEAD;
+  char* zero = G + gbytes;
+  if (N > 0) {
+    G3_HIP(hipMemsetAsync(zero, 0, (size_t)N * es, ctx->stream));
+    const unsigned gx = (unsigned)((N + 255) / 256);
+    int64_t gy = 16384 / gx;
+    gy = gy < 1 ? 1 : (gy > N ? N : gy);
+    g3_by_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((vjp_weight_kernel<T>), dim3(gx, (unsigned)gy), dim3(256), 0, ctx->stream, (T*)G, N, (const T*)Kbar_dev, ldk, N);
+    });
+    G3_LAUNCH_CHECK();
+  }
+  return g3i_gram_grad(ctx, prog, map, X_dev, N, ldx, d, dt, G, N, zero, out_host);
+}
+
 // Fused: K^-1 and alpha from a factor produced by g3_gp_factor, then the hyper-parameter sums.
 extern "C" int g3_gp_dlogp(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev,
                            int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl, const void* invd_dev,

@@ -507,6 +507,21 @@ class Device:
                                         self._ptr(Y), alpha.ptr, kdiag.ptr)
         _check(self, rc, 'g3_gp_loo_batched')
 
+    # ---- reverse mode through the factor (CholeskyRobust.grad, tensors.py:224-260)
+    def potrf_vjp(self, L, Lbar, n, Kbar):
+        """Kbar (n x n: lower triangle, zeros above) <- the covariance adjoint of Lbar = d f / d L at the factor L; only
+        the lower triangles of L and Lbar are read; stream-ordered, the caller downloads"""
+        rc = self.lib.g3_potrf_vjp(self.ctx, L.ptr, L.ld, Lbar.ptr, Lbar.ld, n, _lib.dtype_code(L.dtype), Kbar.ptr, Kbar.ld)
+        _check(self, rc, 'g3_potrf_vjp')
+
+    def gram_vjp(self, prog, gmap, X, N, d, Kbar):
+        """sum over the lower triangle of Kbar_ij d prog(x_i, x_j) / d param per slot of gmap"""
+        out = (C.c_double * max(gmap.nslots, 1))()
+        rc = self.lib.g3_gram_vjp(self.ctx, C.byref(prog), C.byref(gmap), X.ptr, N, X.ld, d, _lib.dtype_code(Kbar.dtype),
+                                  Kbar.ptr, Kbar.ld, out)
+        _check(self, rc, 'g3_gram_vjp')
+        return np.array(out[:gmap.nslots])
+
 
 atexit.register(Device.close_all)
 

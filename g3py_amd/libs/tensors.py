@@ -86,10 +86,12 @@ def tt_to_bounded(r, lower=None, upper=None):
 
 
 class CholeskyRobust:
-    """The Op protocol of tensors.py:174-263 reduced to what the path uses: calling the
-    object, `perform(node, inputs, output_storage)` and `infer_shape`.  The reverse-mode `grad`
-    (tensors.py:224-260) has no symbolic graph to act on here: the product path evaluates the
-    gradient of logp in closed form on the device (`GaussianProcess.th_dlogp`, `g3_gp_dlogp`)."""
+    """The Op protocol of tensors.py:174-263 on NumPy arrays: calling the object,
+    `perform(node, inputs, output_storage)`, `infer_shape` and the reverse-mode `grad(inputs, gradients)`
+    (tensors.py:224-260), all on the device.  There is no symbolic graph here: `grad` maps the
+    array d f / d L to the array d f / d K (`g3_potrf_vjp`); the product path still evaluates the gradient
+    of logp in closed form (`GaussianProcess.th_dlogp`, `g3_gp_dlogp`), and `factor_vjp` of the
+    processes chains `grad` to the kernel hyper-parameters for any other function of the factor."""
     __props__ = ('lower', 'destructive')
 
     def __init__(self, device=None):
@@ -121,8 +123,22 @@ class CholeskyRobust:
         return self._cholesky(x)
 
     def grad(self, inputs, gradients):
-        raise NotImplementedError('no symbolic graph: use GaussianProcess.dlogp (g3_gp_dlogp), which evaluates the '
-                                  'chain through CholeskyRobust.grad (tensors.py:224-260) in closed form')
+        """[Kbar] for Lbar = gradients[0] (tensors.py:224-260): tril(S + S^T) - diag(S) with
+        S = L^-T Phi(tt_to_num(L^T Lbar)) L^-1, on the device (g3_potrf_vjp).  L = self(x) -- the possibly jittered or
+        fallback factor, which the reference re-uses the same way (:238).  The strict upper triangle of Lbar is not read."""
+        x = np.asarray(inputs[0])
+        L = self(x)
+        n = L.shape[0]
+        Lbar = _as2d(gradients[0], L.dtype)
+        if Lbar.shape != L.shape:
+            raise ValueError('gradient of shape %s for a factor of shape %s' % (Lbar.shape, L.shape))
+        if n == 0:
+            return [L.copy()]
+        dev = self.device or Device.default()
+        Ld, Bd = dev.upload(L), dev.upload(Lbar)
+        Kb = dev.alloc(n, n, L.dtype)
+        dev.potrf_vjp(Ld, Bd, n, Kb)
+        return [dev.download(Kb)]
 
 
 cholesky_robust = CholeskyRobust()

@@ -208,7 +208,6 @@ class FactorLikelihood:
         """host part of d loglike: route the device's per-leaf parameter sums (`slots`) to the model's variables and add
         the O(N) location / warping terms on alpha = s K^-1 delta.  slots (nslots,) and alpha (N,) for one row of values,
         (B, nslots) and (B, N) for a chain block; rows with ok False get no likelihood term"""
-        from ..device import spec_leaves, LEAF_FIELDS as fields
         by_name = {v.name: v for v in self.model.vars}
         lead = alpha.shape[:-1]
         if ok is not None:
@@ -217,20 +216,7 @@ class FactorLikelihood:
 
         def add(name, g):            # g: lead for a scalar hyper, lead + (size,) otherwise
             nat[name] = nat[name] + (g if np.shape(g) == nat[name].shape else np.reshape(g, nat[name].shape))
-        # kernel hypers: leaf parameter slots -> the HyperVars that fed them (the alpha slot of a dot leaf is its bias)
-        refs = spec_leaves(self.f_kernel_noise.spec(_Refs(), d))
-        for l, lf in enumerate(refs):
-            nd = prog.leaf[l].ndims
-            for pname, idx in dict(var=1, **fields[lf[0]]).items():
-                ref = lf[idx]
-                if not isinstance(ref, _Ref) or ref.name not in by_name:
-                    continue
-                slot = getattr(gmap, pname)[l]
-                if pname in ('var', 'alpha'):
-                    add(ref.name, slots[..., slot])
-                else:
-                    gk = slots[..., slot:slot + nd]
-                    add(ref.name, gk if by_name[ref.name].shape else gk.sum(axis=-1))
+        self._kernel_slots(nat, prog, gmap, slots, d)
         # location: alpha . d m / d hyper.  Over a chain block d m / d hyper is the same for every row for the means on the
         # path (linear in their hypers, JAC_CONSTANT); any other mean is asked row by row
         if not lead or getattr(self.f_location, 'JAC_CONSTANT', False):
@@ -250,6 +236,60 @@ class FactorLikelihood:
                 if getattr(h, 'name', None) in by_name:
                     g = -(alpha * np.asarray(dinv, dtype=np.float64)).sum(axis=-1) + np.asarray(dlogdet, dtype=np.float64)
                     add(h.name, g if ok is None else np.where(ok, g, 0.0))
+
+    def _kernel_slots(self, nat, prog, gmap, slots, d):
+        """the kernel-hyper part of the chain rule: add the device's per-leaf parameter sums -- slots (nslots,), or
+        (B, nslots) for a chain block -- to the natural-space gradients of the HyperVars that fed them (the alpha slot of a
+        dot leaf is its bias)"""
+        from ..device import spec_leaves, LEAF_FIELDS as fields
+        by_name = {v.name: v for v in self.model.vars}
+        refs = spec_leaves(self.f_kernel_noise.spec(_Refs(), d))
+        for l, lf in enumerate(refs):
+            nd = prog.leaf[l].ndims
+            for pname, idx in dict(var=1, **fields[lf[0]]).items():
+                ref = lf[idx]
+                if not isinstance(ref, _Ref) or ref.name not in by_name:
+                    continue
+                slot = getattr(gmap, pname)[l]
+                if pname in ('var', 'alpha'):
+                    g = slots[..., slot]
+                else:
+                    g = slots[..., slot:slot + nd]
+                    g = g if by_name[ref.name].shape else g.sum(axis=-1)
+                nat[ref.name] = nat[ref.name] + (g if np.shape(g) == nat[ref.name].shape else np.reshape(g, nat[ref.name].shape))
+
+    def factor_vjp(self, params, Lbar, inputs=None, outputs=None):
+        """Reverse mode through the factor for ANY function f of it: given Lbar = d f / d L at the Cholesky factor L of the
+        observed (noisy, possibly jittered) covariance, the gradient of f with respect to the model's variables as dlogp
+        returns one -- flat, in creation order, transformed space, tt_to_num'ed.  Lbar is an N x N array (its strict upper
+        triangle is not read) or a callable L -> Lbar that is handed the downloaded factor.  The device pulls Lbar back to
+        the covariance (g3_potrf_vjp: CholeskyRobust.grad, tensors.py:224-260) and the covariance adjoint to the kernel
+        parameters (g3_gram_vjp: what tt.grad through Kernel.cov does); the jitter is a constant, as in dlogp.  Variables
+        the covariance does not depend on (location, mapping, degrees of freedom) get 0: their part of f's gradient does
+        not pass through L.  A `logp` on the same parameters before it is not repeated."""
+        if self._dist is not None:
+            raise _lib.G3Error('factor_vjp runs on one GPU')
+        if inputs is None and not self.is_observed:
+            raise _lib.G3Error('factor_vjp needs observations')
+        params, _, inputs, outputs, _ = self._call_defaults(params, None, inputs, outputs, False, False)
+        dev = self.device
+        values, _ = self._values(params)
+        c = self._factor(values, inputs, outputs)
+        self._solve(c, values, 'logp')
+        N, d = c['N'], c['d']
+        if callable(Lbar):
+            Lbar = Lbar(np.tril(dev.download(c['Kd'], N, N)))
+        Lbar = np.asarray(Lbar, dtype=self.dtype)
+        if Lbar.shape != (N, N):
+            raise ValueError('Lbar of shape %s for a factor of shape %s' % (Lbar.shape, (N, N)))
+        Bd, Kb = dev.upload(Lbar), dev.alloc(N, N, self.dtype)
+        dev.potrf_vjp(c['Kd'], Bd, N, Kb)
+        prog = self._prog(self.f_kernel_noise, values, d)
+        gmap = dev.grad_layout(prog)
+        slots = dev.gram_vjp(prog, gmap, c['Xd'], N, d, Kb)
+        nat = {v.name: np.zeros(tuple(v.shape)) for v in self.model.vars}
+        self._kernel_slots(nat, prog, gmap, slots, d)
+        return self._flat_gradient(values, nat)
 
     def _flat_gradient(self, values, nat, B=None):
         """natural-space gradients -> flat vector in creation order, transformed space, tt_to_num'ed: (ndim,), or

@@ -437,6 +437,29 @@ int g3_gp_loo(g3_ctx* ctx, const void* L_dev, int64_t N, int64_t ldl, const void
 int g3_gp_loo_batched(g3_ctx* ctx, int batch, const void* L_dev, int64_t N, int64_t ldl, int64_t kstride, const void* invd_dev,
                       const void* a_dev, g3_dtype dt, void* Y_dev, void* alpha_dev, void* kdiag_dev);
 
+/* ---- reverse mode through the Cholesky factor ------------------------------------------------------------------------------
+ * CholeskyRobust.grad (g3py/libs/tensors.py:224-260, Murray 2016): given the factor L (lower) and Lbar = d f / d L,
+ *     Kbar = tril(S + S^T) - diag(S),   S = L^-T Phi(tt_to_num(L^T Lbar)) L^-1,   Phi = tril with halved diagonal
+ * (tril_and_halve_diagonal :245-247, conjugate_solve_triangular :249-252, the lower convention of :258).  L, Lbar and Kbar
+ * are n x n for any n >= 0 (padding to roundup(n,128) is internal, as in g3_potrf_robust).  Only the lower triangles of L and
+ * Lbar are read -- the strict upper triangle of Lbar cannot influence the result and may hold NaN -- and neither is modified.
+ * The lower triangle of Kbar is written and its strict upper triangle is written as zeros; nothing outside those n x n
+ * elements is touched.  Kbar may not overlap L or Lbar (-8).  Y = L^-T comes from g3_potri's sweep without the K^-1 product
+ * (n^3 / 3 flops), the rest is four MFMA products: 5 1/3 n^3 flops in all, in four roundup(n,128)-square matrices of the
+ * context's workspace (G3_ERR_NOMEM when it cannot be had).  Stream-ordered, no host synchronisation; the result is bitwise
+ * reproducible from call to call. */
+int g3_potrf_vjp(g3_ctx* ctx, const void* L_dev, int64_t ldl, const void* Lbar_dev, int64_t ldb, int64_t n, g3_dtype dt,
+                 void* Kbar_dev, int64_t ldk);
+
+/* out_host[slot] = sum_{i >= j, i,j < N} Kbar_ij * d prog(x_i, x_j) / d param(slot)   (square case: NOISE / WN leaves on the
+ * diagonal, kernels.py:360-385): what tt.grad through Kernel.cov (kernels.py:48-49,106-110) does with the lower-triangular
+ * Kbar that CholeskyRobust.grad returns (tensors.py:258).  Only the lower triangle of Kbar_dev is read.  The launches are
+ * g3_gram_grad's, with alpha = 0 and the weight -Kbar (diagonal doubled) written into the context's workspace by one small
+ * pass, so the summation order is its fixed one (bitwise reproducible) and g3_grad_path_stats counts them.  Synchronises,
+ * like g3_gram_grad. */
+int g3_gram_vjp(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev, int64_t N, int64_t ldx,
+                int d, g3_dtype dt, const void* Kbar_dev, int64_t ldk, double* out_host);
+
 /* g3_gp_cross for every member of a chain, after ONE g3_gp_factor_batched(_fields) call with the same member layout
  * (factors kstride elements apart in L_dev with leading dimension ldl, block inverses roundup(N,128)*128 apart, a_dev batch
  * x roundup(N,128)): what the reference's average / particles loop over the rows of a trace for
