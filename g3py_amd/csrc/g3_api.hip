@@ -5,7 +5,7 @@
 #include <stdlib.h>
 
 // ----------------------------------------------------------------------------- context
-extern "C" int g3_version(void) { return 103; }
+extern "C" int g3_version(void) { return 104; }
 
 static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out);
 extern "C" int g3_ctx_create(int device, g3_ctx** out) { return ctx_create_impl(device, nullptr, out); }

@@ -1104,6 +1104,7 @@ static int check_map(const g3_kernel_prog* prog, const g3_grad_map* map) {
   }
   return 0;
 }
+int g3i_check_map(const g3_kernel_prog* prog, const g3_grad_map* map) { return check_map(prog, map); }
 
 extern "C" int g3_gram_grad(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev,
                             int64_t N, int64_t ldx, int d, g3_dtype dt, const void* G_dev, int64_t ldg,
@@ -1152,6 +1153,15 @@ extern "C" int g3_gram_grad_rows(g3_ctx* ctx, const g3_kernel_prog* prog, const 
 // sum_{i >= j} Kbar_ij dK_ij / dparam.  G and the zero alpha live in the context's workspace BEHIND the part the three paths
 // use for their partial sums and outputs: for one member at most 4096 workgroups x 52 slots x 8 B and 4.2 KB, under 2 MiB.
 #define GG_VJP_HEAD ((size_t)4 << 20)
+// The same bound for `batch` members: a member's tiles are walked by at most ceil(8192 / batch) workgroups, so all members
+// together have fewer than 8192 + batch; at most 52 slots (64 taken) of partial sums each, one output row of at most
+// roundup(G3_GRAD_MAXSLOTS, 32) doubles and one program (or, smaller, one SeGradParams) per member.
+size_t g3i_gram_grad_head(int batch) {
+  if (batch <= 1) return GG_VJP_HEAD;
+  const size_t per_member = sizeof(g3_kernel_prog) > sizeof(SeGradParams<16>) ? sizeof(g3_kernel_prog) : sizeof(SeGradParams<16>);
+  const size_t orow = (size_t)g3_roundup(G3_GRAD_MAXSLOTS > 64 ? G3_GRAD_MAXSLOTS : 64, 32) * sizeof(double);
+  return (size_t)g3_roundup((int64_t)(((size_t)8192 + batch) * 64 * sizeof(double) + (size_t)batch * (orow + per_member)), 256);
+}
 template <typename T>
 __global__ void __launch_bounds__(256)
 vjp_weight_kernel(T* __restrict__ G, int64_t ldg, const T* __restrict__ Kbar, int64_t ldk, int64_t n) {

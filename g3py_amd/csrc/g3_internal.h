@@ -272,6 +272,11 @@ hipFunction_t g3i_grad_jit_function(g3_ctx* ctx, const g3_kernel_prog* prog_host
 int g3i_gram_grad_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const g3_grad_map* map, const void* X, int64_t N,
                           int64_t ldx, int d, g3_dtype dt, const void* G, int64_t ldg, int64_t gstride, const void* alpha,
                           int64_t astride, double* out_host, int64_t row0 = 0, int64_t nrows = -1);
+// 0 = every slot of `map` lies inside [0, nslots) for prog's leaves (the gradient entry points' check of their map argument)
+int g3i_check_map(const g3_kernel_prog* prog, const g3_grad_map* map);
+// bytes at the head of the context's workspace that g3i_gram_grad_batched may use for `batch` members (partial sums,
+// outputs, member programs): a weight matrix kept in the workspace across that call starts behind them
+size_t g3i_gram_grad_head(int batch);
 int g3i_rows_dot_ss_batched(g3_ctx* ctx, const void* V, int64_t m, int64_t n, int64_t ld, const void* a, g3_dtype dt, void* dot,
                             void* ss, int batch, int64_t vstride, int64_t astride, int64_t ostride);
 // rows_dot_ss over the upper triangle of a square Y (npad x npad): rows [0, n) from their diagonal on, rows [n, npad) get 0

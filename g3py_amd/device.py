@@ -507,6 +507,25 @@ class Device:
                                         self._ptr(Y), alpha.ptr, kdiag.ptr)
         _check(self, rc, 'g3_gp_loo_batched')
 
+    # ---- gradient of the leave-one-out log predictive
+    def gp_dloo(self, prog, gmap, X, N, d, L, W, a, Y, Kinv, alpha, kdiag, u):
+        """after gp_factor: K^-1, alpha = K^-1 delta, kdiag = diag K^-1, u = K^-1 (alpha / kdiag) (roundup(N) entries each,
+        0 from N on) and sum_ij W_ij dK_ij/dparam per slot, W the covariance adjoint of the leave-one-out score"""
+        out = (C.c_double * max(gmap.nslots, 1))()
+        rc = self.lib.g3_gp_dloo(self.ctx, C.byref(prog), C.byref(gmap), X.ptr, N, X.ld, d, L.ptr, L.ld, W.ptr, a.ptr,
+                                 _lib.dtype_code(L.dtype), Y.ptr, Y.ld, Kinv.ptr, Kinv.ld, alpha.ptr, kdiag.ptr, u.ptr, out)
+        _check(self, rc, 'g3_gp_dloo')
+        return np.array(out[:gmap.nslots])
+
+    def gp_dloo_batched_fields(self, tmpl, offsets, fields, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha, kdiag, u):
+        """gp_dloo for members given as template + fields (after gp_factor_batched_fields on the same buffers); alpha,
+        kdiag and u are (B, roundup(N)) device matrices; returns (B, nslots)"""
+        B, members = self._fields_args('gp_dloo_batched_fields', tmpl, offsets, fields)
+        out, args = self._dlogp_args(B, gmap, X, N, d, K, kstride, W, a, Y, Kinv, alpha)
+        _check(self, self.lib.g3_gp_dloo_batched_fields(self.ctx, *members, *args[:-1], kdiag.ptr, u.ptr, args[-1]),
+               'g3_gp_dloo_batched_fields')
+        return out[:, :gmap.nslots]
+
     # ---- reverse mode through the factor (CholeskyRobust.grad, tensors.py:224-260)
     def potrf_vjp(self, L, Lbar, n, Kbar):
         """Kbar (n x n: lower triangle, zeros above) <- the covariance adjoint of Lbar = d f / d L at the factor L; only

@@ -706,6 +706,82 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
                     buf.free()
         return out
 
+    def dloo(self, params=None, inputs=None, outputs=None):
+        """Gradient of loo(...).logpredictive with respect to the model's variables, as dlogp returns one: flat, in creation
+        order, transformed space, tt_to_num'ed.  A predictive score: no prior, Jacobian or potential terms.  With A = K^-1 of
+        the factored (possibly jittered, the jitter a constant) noisy covariance, alpha = A delta and c = diag A,
+            d F = sum_ij W_ij dK_ij + u . dm - u . dT^-1(y) + d logdet,
+            W = -A diag(q) A + 1/2 (u alpha^T + alpha u^T),  q = 1/2 (1 / c + alpha^2 / c^2),  u = A (alpha / c);
+        the device forms K^-1, the weight and the kernel-parameter sums (g3_gp_dloo: about 1 2/3 N^3 flops), the host the O(N)
+        location and warping terms -- dlogp's chain rule with u in the place of alpha.  Zeros where loo returns its -1e30
+        sentinel.  A `logp` on the same parameters before it is not repeated; the K^-1 workspaces are dlogp's."""
+        self._loo_guard(inputs)
+        params, _, inputs, outputs, _ = self._call_defaults(params, None, inputs, outputs, False, False)
+        dev = self.device
+        values, _ = self._values(params)
+        nat = {v.name: np.zeros(tuple(v.shape)) for v in self.model.vars}
+        c = self._factor(values, inputs, outputs)
+        if not (np.all(np.isfinite(c['delta'])) and np.all(np.isfinite(c['det_m']))):          # gaussian.py:234-235
+            return self._flat_gradient(values, nat)
+        st = self._solve(c, values, 'logp')
+        if not np.isfinite(st['logdet']) or st['nonfinite'] > 0:                                # gaussian.py:237
+            return self._flat_gradient(values, nat)
+        N, d, Np = c['N'], c['d'], c['Np']
+        g = c.get('dloo')
+        if g is None or g['stats'] is not st:        # (kept with the factorisation it belongs to)
+            prog = self._prog(self.f_kernel_noise, values, d)
+            gmap = dev.grad_layout(prog)
+            ws = self._workspace
+            if 'Y' not in ws:                        # (Y, Kinv and alpha: dlogp's, scratch in both)
+                ws['Y'] = dev.alloc(Np, Np, self.dtype)
+            if 'Kinv' not in ws:
+                ws['Kinv'], ws['alpha'] = dev.alloc(Np, Np, self.dtype), dev.alloc(1, Np, self.dtype)
+            if 'dloo' not in ws:
+                ws['dloo'] = dev.alloc(2, Np, self.dtype)        # kdiag, u
+            vec = ws['dloo']
+            slots = dev.gp_dloo(prog, gmap, c['Xd'], N, d, c['Kd'], c['Wd'], c['ad'], ws['Y'], ws['Kinv'], ws['alpha'], vec,
+                                dev.wrap(vec.offset(1), 1, Np, Np, self.dtype, keep=vec))
+            g = c['dloo'] = dict(stats=st, prog=prog, gmap=gmap, slots=slots, u=dev.download(vec, 2, N)[1].astype(np.float64))
+        self._chain_rule(values, c['X'], c['y'], nat, g['prog'], g['gmap'], g['slots'], g['u'], d)
+        return self._flat_gradient(values, nat)
+
+    def dloo_chain(self, chain, batch=None):
+        """one dloo per row of a flat-parameter chain, shape (rows, ndim).  The block structure and the workspace are
+        dlogp_chain's: `batch` rows share ONE Gram launch, ONE factorisation sweep and ONE K^-1 sweep, then the members'
+        weights, products and kernel-parameter sums in launches that carry the member in the grid
+        (g3_gp_dloo_batched_fields); the chain rule is array arithmetic over the rows.  Rows that loo_chain sends to its
+        -1e30 sentinel get zeros."""
+        self._loo_guard()
+        chain = np.atleast_2d(np.asarray(chain, dtype=np.float64))
+        n_rows = len(chain)
+        out = np.zeros((n_rows, self.active.ndim), dtype=self.dtype)
+        if n_rows == 0:
+            return out
+        dev = self.device
+        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
+            n_rows, batch, lambda Np, kstride: int(4e9 // (3 * kstride * self.dtype.itemsize)), grad=True)
+        K, Y, Ki, W, a, al = ws['K'], ws['Y'], ws['Ki'], ws['W'], ws['a'], ws['al']
+        vec = dev.alloc(2 * batch, Np, self.dtype)               # a block's kdiag rows, then its u rows
+        try:
+            for lo in range(0, n_rows, batch):
+                hi = min(lo + batch, n_rows)
+                B = hi - lo
+                values_b, _ = self._values_rows(chain[lo:hi])
+                tmpl, offs, fields = members = self._chain_members(self.f_kernel_noise, values_b, d, B)
+                delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
+                st = self._chain_factor_block(members, delta, Xd, N, d, K, kstride, W, a)
+                gmap = dev.grad_layout(tmpl)
+                ok = ~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0)                           # gaussian.py:234-237
+                ud = dev.wrap(vec.offset(B), B, Np, Np, self.dtype, keep=vec)
+                slots = dev.gp_dloo_batched_fields(tmpl, offs, fields, gmap, Xd, N, d, K, kstride, W, a, Y, Ki, al, vec, ud)
+                nat = {v.name: np.zeros((B,) + tuple(v.shape)) for v in self.model.vars}
+                self._chain_rule(values_b, X, y, nat, tmpl, gmap, slots, dev.download(ud, B, N).astype(np.float64), d, ok)
+                out[lo:hi] = self._flat_gradient(values_b, nat, B)
+        finally:
+            for buf in (vec, Xd):
+                buf.free()
+        return out
+
     # ---- quantiles and draws (gaussian.py:56-97)
     def quantiler(self, params=None, space=None, inputs=None, outputs=None, q=0.975, prior=False, noise=False,
                   simulations=None):

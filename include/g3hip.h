@@ -460,6 +460,39 @@ int g3_potrf_vjp(g3_ctx* ctx, const void* L_dev, int64_t ldl, const void* Lbar_d
 int g3_gram_vjp(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev, int64_t N, int64_t ldx,
                 int d, g3_dtype dt, const void* Kbar_dev, int64_t ldk, double* out_host);
 
+/* ---- gradient of the leave-one-out log predictive with respect to the kernel parameters (no counterpart in the reference) ---
+ * After g3_gp_factor on the same buffers, as g3_gp_dlogp: with A = K^-1 of the factored covariance (its jitter a constant),
+ * alpha = A delta, c = diag A and F = sum_i [1/2 log c_i - 1/2 alpha_i^2 / c_i] (the parameter-dependent part of g3_gp_loo's
+ * score),
+ *     dF = sum_ij W_ij dK_ij - u . d delta,     W = -A diag(q) A + 1/2 (u alpha^T + alpha u^T),
+ *     q_i = 1/2 (1 / c_i + alpha_i^2 / c_i^2),  u = A b,  b_i = alpha_i / c_i.
+ * out_host[slot] = sum_{i,j < N} W_ij d prog(x_i, x_j) / d param(slot) over the full symmetric index range, through
+ * g3_gram_grad's launches with a zero alpha and the weight
+ *     G = -2 W = M M^T - u alpha^T - alpha u^T,   M_ij = A_ij s_j,   s_j = sqrt(c_j + alpha_j^2) / c_j,
+ *     u = M t,   t_j = alpha_j / sqrt(c_j + alpha_j^2).
+ * Steps: g3_potri (Y_dev <- L^-T, lower triangle of Kinv_dev <- K^-1), alpha = Y a, ONE pass over the lower triangle of
+ * Kinv_dev that writes the full square M into the context's workspace together with kdiag and t (nothing above Kinv's
+ * diagonal is read), u = M t, G = M M^T as one lower-triangular MFMA product into Y_dev, the rank-two part as one small pass
+ * over G's lower triangle, and the kernel-parameter sums: about 1 2/3 N^3 flops.  alpha_dev, kdiag_dev (= diag K^-1) and
+ * u_dev have roundup(N,128) entries, the entries from N on written as 0.  On return Kinv_dev holds the lower triangle of K^-1
+ * exactly as g3_gp_dlogp leaves it and Y_dev is unspecified.  Argument checks and their numbering as g3_gp_dlogp's.  The
+ * sums are combined in a fixed order (two calls give the same bits).  Synchronises, like g3_gp_dlogp; G3_ERR_NOMEM when the
+ * workspace (roundup(N,128)^2 elements and 4 MiB) cannot be had. */
+int g3_gp_dloo(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev, int64_t N, int64_t ldx, int d,
+               const void* L_dev, int64_t ldl, const void* invd_dev, const void* a_dev, g3_dtype dt, void* Y_dev, int64_t ldy,
+               void* Kinv_dev, int64_t ldc, void* alpha_dev, void* kdiag_dev, void* u_dev, double* out_host);
+/* The same for every member of a chain, after g3_gp_factor_batched(_fields), with the arguments of
+ * g3_gp_dlogp_batched_fields: Y_dev and Kinv_dev hold `batch` members kstride apart (ld = ldl), alpha_dev, kdiag_dev and u_dev
+ * are batch x roundup(N,128), out_host is batch x map->nslots.  The K^-1 sweep, the products and the sums carry the member in
+ * the grid; the members' M live in the context's workspace, at most 256 MB of it per launch group (longer chains take several
+ * groups).  A member that went through the jitter schedule is differentiated at the factor that was kept.  batch <= 4096.
+ * Argument numbers in negative return codes follow this signature. */
+int g3_gp_dloo_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl_host, int batch, const double* fields_host,
+                              const int32_t* offsets_host, int nfield, const g3_grad_map* map, const void* X_dev, int64_t N,
+                              int64_t ldx, int d, const void* L_dev, int64_t ldl, int64_t kstride, const void* invd_dev,
+                              const void* a_dev, g3_dtype dt, void* Y_dev, void* Kinv_dev, void* alpha_dev, void* kdiag_dev,
+                              void* u_dev, double* out_host);
+
 /* g3_gp_cross for every member of a chain, after ONE g3_gp_factor_batched(_fields) call with the same member layout
  * (factors kstride elements apart in L_dev with leading dimension ldl, block inverses roundup(N,128)*128 apart, a_dev batch
  * x roundup(N,128)): what the reference's average / particles loop over the rows of a trace for
