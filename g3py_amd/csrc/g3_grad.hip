@@ -1,4 +1,5 @@
-// Gradient of the GP log marginal likelihood with respect to the kernel hyper-parameters.
+// Gradient of the GP log marginal likelihood with respect to the kernel hyper-parameters: the K^-1 sweep and the kernel-parameter
+// sums (g3_potri, g3_gram_grad, _rows, g3_gram_vjp); g3_gp_grad.hip fuses them on a finished factor (g3_gp_dlogp*, g3_gp_dloo*).
 //
 // Reference: StochasticProcess.th_dlogp = gradient(th_logp) (g3py/processes/stochastic.py:308-309,
 // g3py/libs/tensors.py:11-22) -- Theano differentiates logp_cho (gaussian.py:208-224) through
@@ -13,7 +14,6 @@
 //                    the kernel expression per pair and accumulates G_ij * d k_ij / d theta for
 //                    every parameter of every leaf; deterministic two-stage reduction.
 #include "g3_internal.h"
-#include <optional>
 #include <vector>
 #include <stdlib.h>
 
@@ -162,7 +162,7 @@ extern "C" int g3_potri(g3_ctx* ctx, const void* L_dev, int64_t n, int64_t ldl, 
 extern "C" int g3_grad_layout(const g3_kernel_prog* prog, g3_grad_map* map) {
   if (!prog) return -1;
   if (!map) return -2;
-  if (prog->nleaf < 0 || prog->nleaf > G3_MAXLEAF) return -1;
+  if (g3h_nleaf_bad(prog)) return -1;
   int s = 0;
   for (int l = 0; l < G3_MAXLEAF; ++l) map->var[l] = map->alpha[l] = map->rate[l] = map->freq[l] = -1;
   for (int l = 0; l < prog->nleaf; ++l) {
@@ -1093,30 +1093,19 @@ int g3i_gram_grad(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* ma
   return g3i_gram_grad_batched(ctx, prog, 1, map, X, N, ldx, d, dt, G, ldg, 0, alpha, 0, out_host, row0, nrows);
 }
 
-static int check_map(const g3_kernel_prog* prog, const g3_grad_map* map) {
-  if (map->nslots < 0 || map->nslots > G3_GRAD_MAXSLOTS) return 1;
-  for (int l = 0; l < prog->nleaf; ++l) {
-    const int nd = prog->leaf[l].ndims;
-    const int32_t v[4] = {map->var[l], map->alpha[l], map->rate[l], map->freq[l]};
-    const int w[4] = {1, 1, nd, nd};
-    for (int q = 0; q < 4; ++q)
-      if (v[q] < -1 || (v[q] >= 0 && v[q] + w[q] > map->nslots)) return 1;
-  }
-  return 0;
+// the arguments (prog, map, X, N, ldx, d) that g3_gram_grad, g3_gram_grad_rows and g3_gram_vjp start with, at 2 .. 7
+static int gram_grad_args(const g3_kernel_prog* prog, const g3_grad_map* map, const void* X, int64_t N, int64_t ldx, int d) {
+  const int rc = g3h_args_prog(prog, map, 2);
+  return rc ? rc : g3h_args_inputs(X, N, ldx, d, 4, true);
 }
-int g3i_check_map(const g3_kernel_prog* prog, const g3_grad_map* map) { return check_map(prog, map); }
 
 extern "C" int g3_gram_grad(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev,
                             int64_t N, int64_t ldx, int d, g3_dtype dt, const void* G_dev, int64_t ldg,
                             const void* alpha_dev, double* out_host) {
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
-  if (!prog || prog->nleaf < 0 || prog->nleaf > G3_MAXLEAF || prog->nprod < 0 || prog->nprod > G3_MAXPROD) return -2;
-  if (!map || check_map(prog, map)) return -3;
-  if (!X_dev && N > 0) return -4;
-  if (N < 0) return -5;
-  if (d < 1 || d > G3_MAXCOLS) return -7;
-  if (ldx < d) return -6;
+  const int rc = gram_grad_args(prog, map, X_dev, N, ldx, d);
+  if (rc) return rc;
   if (!G_dev && N > 0) return -9;
   if (ldg < N) return -10;
   if (!alpha_dev && N > 0) return -11;
@@ -1131,12 +1120,8 @@ extern "C" int g3_gram_grad_rows(g3_ctx* ctx, const g3_kernel_prog* prog, const 
                                  const void* G_rows_dev, int64_t ldg, const void* alpha_dev, double* out_host) {
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
-  if (!prog || prog->nleaf < 0 || prog->nleaf > G3_MAXLEAF || prog->nprod < 0 || prog->nprod > G3_MAXPROD) return -2;
-  if (!map || check_map(prog, map)) return -3;
-  if (!X_dev && N > 0) return -4;
-  if (N < 0) return -5;
-  if (d < 1 || d > G3_MAXCOLS) return -7;
-  if (ldx < d) return -6;
+  const int rc = gram_grad_args(prog, map, X_dev, N, ldx, d);
+  if (rc) return rc;
   if (row0 < 0 || row0 % GG_T) return -9;
   if (nrows < 0 || row0 + nrows > N) return -10;
   if (!G_rows_dev && nrows > 0) return -11;
@@ -1152,16 +1137,25 @@ extern "C" int g3_gram_grad_rows(g3_ctx* ctx, const g3_kernel_prog* prog, const 
 // that weight is Kbar_ij exactly (0 - x and the factor 1/2 * 2 round nothing), so the same launches in the same order give
 // sum_{i >= j} Kbar_ij dK_ij / dparam.  G and the zero alpha live in the context's workspace BEHIND the part the three paths
 // use for their partial sums and outputs: for one member at most 4096 workgroups x 52 slots x 8 B and 4.2 KB, under 2 MiB.
-#define GG_VJP_HEAD ((size_t)4 << 20)
 // The same bound for `batch` members: a member's tiles are walked by at most ceil(8192 / batch) workgroups, so all members
 // together have fewer than 8192 + batch; at most 52 slots (64 taken) of partial sums each, one output row of at most
 // roundup(G3_GRAD_MAXSLOTS, 32) doubles and one program (or, smaller, one SeGradParams) per member.
-size_t g3i_gram_grad_head(int batch) {
-  if (batch <= 1) return GG_VJP_HEAD;
+static size_t gram_grad_head(int batch) {
+  if (batch <= 1) return (size_t)4 << 20;
   const size_t per_member = sizeof(g3_kernel_prog) > sizeof(SeGradParams<16>) ? sizeof(g3_kernel_prog) : sizeof(SeGradParams<16>);
   const size_t orow = (size_t)g3_roundup(G3_GRAD_MAXSLOTS > 64 ? G3_GRAD_MAXSLOTS : 64, 32) * sizeof(double);
   return (size_t)g3_roundup((int64_t)(((size_t)8192 + batch) * 64 * sizeof(double) + (size_t)batch * (orow + per_member)), 256);
 }
+int g3i_reserve_behind_grad(g3_ctx* ctx, int batch, size_t bytes, char** behind) {
+  const size_t head = gram_grad_head(batch);
+  if (g3i_ensure_work(ctx, head + bytes) != G3_OK) {
+    (void)hipGetLastError();
+    return G3_ERR_NOMEM;
+  }
+  *behind = (char*)ctx->work + head;
+  return G3_OK;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 vjp_weight_kernel(T* __restrict__ G, int64_t ldg, const T* __restrict__ Kbar, int64_t ldk, int64_t n) {
@@ -1175,144 +1169,27 @@ extern "C" int g3_gram_vjp(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_gra
                            int64_t ldx, int d, g3_dtype dt, const void* Kbar_dev, int64_t ldk, double* out_host) {
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
-  if (!prog || prog->nleaf < 0 || prog->nleaf > G3_MAXLEAF || prog->nprod < 0 || prog->nprod > G3_MAXPROD) return -2;
-  if (!map || check_map(prog, map)) return -3;
-  if (!X_dev && N > 0) return -4;
-  if (N < 0) return -5;
-  if (d < 1 || d > G3_MAXCOLS) return -7;
-  if (ldx < d) return -6;
+  int rc = gram_grad_args(prog, map, X_dev, N, ldx, d);
+  if (rc) return rc;
   if (dt != G3_F64 && dt != G3_F32) return -8;
   if (!Kbar_dev && N > 0) return -9;
   if (ldk < N) return -10;
   if (!out_host) return -11;
   const size_t es = g3_esize(dt);
   const size_t gbytes = (size_t)g3_roundup((int64_t)((size_t)N * N * es), 256);
-  if (g3i_ensure_work(ctx, GG_VJP_HEAD + gbytes + (size_t)N * es) != G3_OK) {
-    (void)hipGetLastError();
-    return G3_ERR_NOMEM;
-  }
-  char* G = (char*)ctx->work + GG_VJP_HEAD;
+  char* G;
+  rc = g3i_reserve_behind_grad(ctx, 1, gbytes + (size_t)N * es, &G);
+  if (rc) return rc;
   char* zero = G + gbytes;
   if (N > 0) {
     G3_HIP(hipMemsetAsync(zero, 0, (size_t)N * es, ctx->stream));
-    const unsigned gx = (unsigned)((N + 255) / 256);
-    int64_t gy = 16384 / gx;
-    gy = gy < 1 ? 1 : (gy > N ? N : gy);
     g3_by_dtype(dt, [&](auto t) {
       using T = decltype(t);
-      hipLaunchKernelGGL((vjp_weight_kernel<T>), dim3(gx, (unsigned)gy), dim3(256), 0, ctx->stream, (T*)G, N, (const T*)Kbar_dev, ldk, N);
+      hipLaunchKernelGGL((vjp_weight_kernel<T>), g3_tril_rows_grid(N), dim3(256), 0, ctx->stream, (T*)G, N, (const T*)Kbar_dev, ldk, N);
     });
     G3_LAUNCH_CHECK();
   }
   return g3i_gram_grad(ctx, prog, map, X_dev, N, ldx, d, dt, G, N, zero, out_host);
-}
-
-// Fused: K^-1 and alpha from a factor produced by g3_gp_factor, then the hyper-parameter sums.
-extern "C" int g3_gp_dlogp(g3_ctx* ctx, const g3_kernel_prog* prog, const g3_grad_map* map, const void* X_dev,
-                           int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl, const void* invd_dev,
-                           const void* a_dev, g3_dtype dt, void* Y_dev, int64_t ldy, void* Kinv_dev, int64_t ldc,
-                           void* alpha_dev, double* out_host) {
-  if (!ctx) return -1;
-  g3_dev_guard _dg(ctx);
-  if (!prog || prog->nleaf < 0 || prog->nleaf > G3_MAXLEAF || prog->nprod < 0 || prog->nprod > G3_MAXPROD) return -2;
-  if (!map || check_map(prog, map)) return -3;
-  if (!X_dev) return -4;
-  if (N <= 0) return -5;
-  if (d < 1 || d > G3_MAXCOLS) return -7;
-  if (ldx < d) return -6;
-  const int64_t Np = g3_roundup(N, G3_LB), al = 16 / (int64_t)g3_esize(dt);
-  if (!L_dev) return -8;
-  if (ldl < Np || ldl % al) return -9;
-  if (!invd_dev) return -10;
-  if (!a_dev) return -11;
-  if (!Y_dev) return -13;
-  if (ldy < Np || ldy % al) return -14;
-  if (!Kinv_dev) return -15;
-  if (ldc < Np || ldc % al) return -16;
-  if (!alpha_dev) return -17;
-  if (!out_host) return -18;
-  int rc = g3i_reset_info(ctx);
-  if (rc) return rc;
-  int rec = g3i_prof_begin(ctx, G3_TAG_POTRF, 2.0 * (double)N * N * N / 3.0);
-  rc = g3i_potri(ctx, L_dev, Np, ldl, invd_dev, dt, Y_dev, ldy, Kinv_dev, ldc);
-  g3i_prof_end(ctx, rec);
-  if (rc) return rc;
-  // alpha = L^-T a = Y a  (row i of Y dotted with a)
-  rc = g3_rows_dot_ss(ctx, Y_dev, Np, Np, ldy, a_dev, dt, alpha_dev, nullptr);
-  if (rc) return rc;
-  return g3i_gram_grad(ctx, prog, map, X_dev, N, ldx, d, dt, Kinv_dev, ldc, alpha_dev, out_host);
-}
-
-
-// Batched dlogp: `batch` factorisations produced by ONE g3_gp_factor_batched sweep (members kstride
-// elements apart in L_dev, diagonal-block inverses Npad*128 apart, a_dev batch x Npad) -- the caller
-// pattern of fixed_dlogp / find_MAP restarts (g3py/processes/stochastic.py:554-564: a Python loop
-// over single gradients in the reference).  K^-1 of every member comes out of one batched potri
-// sweep (grid.y = member in every MFMA GEMM and diagonal-block launch); the O(N^2) kernel-parameter
-// sums then run member by member.  Y_dev / Kinv_dev: batch members, kstride apart, ld = ldl.
-extern "C" int g3_gp_dlogp_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const g3_grad_map* map,
-                                   const void* X_dev, int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl,
-                                   int64_t kstride, const void* invd_dev, const void* a_dev, g3_dtype dt, void* Y_dev,
-                                   void* Kinv_dev, void* alpha_dev, double* out_host) {
-  if (!ctx) return -1;
-  g3_dev_guard _dg(ctx);
-  if (!progs) return -2;
-  if (batch < 1 || batch > G3_MAX_BATCH) return -3;
-  if (!map) return -4;
-  for (int b = 0; b < batch; ++b) {
-    if (progs[b].nleaf < 0 || progs[b].nleaf > G3_MAXLEAF || progs[b].nprod < 0 || progs[b].nprod > G3_MAXPROD) return -2;
-    if (check_map(&progs[b], map)) return -4;
-  }
-  if (!X_dev) return -5;
-  if (N <= 0) return -6;
-  if (d < 1 || d > G3_MAXCOLS) return -8;
-  if (ldx < d) return -7;
-  const int64_t Np = g3_roundup(N, G3_LB), al = 16 / (int64_t)g3_esize(dt);
-  const size_t es = g3_esize(dt);
-  if (!L_dev) return -9;
-  if (ldl < Np || ldl % al) return -10;
-  if (kstride < Np * ldl || kstride % al) return -11;
-  if (!invd_dev) return -12;
-  if (!a_dev) return -13;
-  if (!Y_dev) return -15;
-  if (!Kinv_dev) return -16;
-  if (!alpha_dev) return -17;
-  if (!out_host) return -18;
-  int rc;
-  {
-    std::optional<g3_batch_scope> mode;       // one member: the plain single-member launches
-    if (batch > 1) mode.emplace(ctx, batch, kstride, Np * G3_LB, invd_dev, (size_t)batch * Np * G3_LB * es);
-    // in batch mode: EVERY member's pivot flag (a member whose first factorisation failed was re-run through the jitter
-    // schedule on its own, and its flag of the batched sweep must not turn this sweep's launches into no-ops for it)
-    rc = g3i_reset_info(ctx);
-    if (rc) return rc;
-    const int rec = g3i_prof_begin(ctx, G3_TAG_POTRF, 2.0 * (double)batch * (double)N * N * N / 3.0);
-    rc = g3i_potri(ctx, L_dev, Np, ldl, invd_dev, dt, Y_dev, ldl, Kinv_dev, ldl);
-    g3i_prof_end(ctx, rec);
-  }
-  if (rc) return rc;
-  // alpha_b = L_b^-T a_b for every member in one launch, then the kernel-parameter sums of all members in launches that
-  // carry the member in grid.y and ONE copy back (a chain of 4096 members: 3 launches instead of 12 288 and 4096 host waits)
-  rc = g3i_rows_dot_ss_batched(ctx, Y_dev, Np, Np, ldl, a_dev, dt, alpha_dev, nullptr, batch, kstride, Np, Np);
-  if (rc) return rc;
-  return g3i_gram_grad_batched(ctx, progs, batch, map, X_dev, N, ldx, d, dt, Kinv_dev, ldl, kstride, alpha_dev, Np, out_host);
-}
-
-// g3_gp_dlogp_batched with the members given as in g3_gp_factor_batched_fields: one template program plus the doubles that
-// differ per member.  (The gradient kernels need each member's parameters on the host side -- fast-path matching -- so the
-// programs are expanded here, 6 KB per member, instead of being packed by the binding.)
-extern "C" int g3_gp_dlogp_batched_fields(g3_ctx* ctx, const g3_kernel_prog* tmpl, int batch, const double* fields,
-                                          const int32_t* offsets, int nfield, const g3_grad_map* map, const void* X_dev,
-                                          int64_t N, int64_t ldx, int d, const void* L_dev, int64_t ldl, int64_t kstride,
-                                          const void* invd_dev, const void* a_dev, g3_dtype dt, void* Y_dev, void* Kinv_dev,
-                                          void* alpha_dev, double* out_host) {
-  if (!ctx) return -1;
-  return g3i_fields_call(tmpl, batch, true, fields, offsets, nfield, -18, [&](const MemberProgs& mp) {
-    std::vector<g3_kernel_prog> progs((size_t)batch);
-    for (int b = 0; b < batch; ++b) mp.member(b, &progs[b]);
-    return g3_gp_dlogp_batched(ctx, progs.data(), batch, map, X_dev, N, ldx, d, L_dev, ldl, kstride, invd_dev, a_dev, dt, Y_dev,
-                               Kinv_dev, alpha_dev, out_host);
-  });
 }
 
 extern "C" int g3_grad_path_stats(g3_ctx* ctx, double out_host[3]) {

@@ -584,9 +584,13 @@ static inline int g3h_match_fast(const g3_kernel_prog* p, int d, SeParams<T, D>*
   return lf.kind;
 }
 
+// the counts of a program outside its tables: all the gradient entry points ask of a program (g3_grad_layout: of its leaves)
+static inline bool g3h_nleaf_bad(const g3_kernel_prog* p) { return p->nleaf < 0 || p->nleaf > G3_MAXLEAF; }
+static inline bool g3h_counts_bad(const g3_kernel_prog* p) { return g3h_nleaf_bad(p) || p->nprod < 0 || p->nprod > G3_MAXPROD; }
+
 // validity of a kernel program for inputs with d columns (every index the device will follow)
 static inline int g3h_validate_prog(const g3_kernel_prog* p, int d) {
-  if (p->nleaf < 0 || p->nleaf > G3_MAXLEAF || p->nprod < 0 || p->nprod > G3_MAXPROD) return 1;
+  if (g3h_counts_bad(p)) return 1;
   for (int l = 0; l < p->nleaf; ++l) {
     const g3_leaf& lf = p->leaf[l];
     if (lf.kind < 0 || lf.kind > G3_K_LAST) return 1;
@@ -684,3 +688,71 @@ static inline G3hMemberLayout g3h_member_layout(int batch, int nfield, int whole
   lo.total = lo.tail + tail_bytes;
   return lo;
 }
+
+// ---- argument checks of the entry points that run on a finished factor or on K^-1 (g3_gp_grad.hip, g3_grad.hip, g3_loo.hip).
+// include/g3hip.h: the status -i says that argument i is invalid.  Each function checks ONE group of arguments as a caller
+// passes it and returns 0 or that status; `at` is the number of the group's first argument, so a batched entry point's groups
+// are the single one's, shifted.  Which status wins when several arguments are bad is part of what callers see: the order
+// inside a group and every entry point's composition are pinned by tests/host_asan/harness.cpp::test_argument_groups.
+#define G3_MAX_BATCH 4096
+// 0 = every slot of `map` lies inside [0, nslots) for prog's leaves
+static inline int g3h_check_map(const g3_kernel_prog* prog, const g3_grad_map* map) {
+  if (map->nslots < 0 || map->nslots > G3_GRAD_MAXSLOTS) return 1;
+  for (int l = 0; l < prog->nleaf; ++l) {
+    const int nd = prog->leaf[l].ndims;
+    const int32_t v[4] = {map->var[l], map->alpha[l], map->rate[l], map->freq[l]};
+    const int w[4] = {1, 1, nd, nd};
+    for (int q = 0; q < 4; ++q)
+      if (v[q] < -1 || (v[q] >= 0 && v[q] + w[q] > map->nslots)) return 1;
+  }
+  return 0;
+}
+// one program and the map of its slots: at, at + 1
+static inline int g3h_args_prog(const g3_kernel_prog* prog, const g3_grad_map* map, int at) {
+  if (!prog || g3h_counts_bad(prog)) return -at;
+  if (!map || g3h_check_map(prog, map)) return -(at + 1);
+  return 0;
+}
+// a chain's programs, their number and the one map: at, at + 1, at + 2 (a missing map is refused before any member is looked at)
+static inline int g3h_args_progs(const g3_kernel_prog* progs, int batch, const g3_grad_map* map, int at) {
+  if (!progs) return -at;
+  if (batch < 1 || batch > G3_MAX_BATCH) return -(at + 1);
+  if (!map) return -(at + 2);
+  for (int b = 0; b < batch; ++b) {
+    if (g3h_counts_bad(&progs[b])) return -at;
+    if (g3h_check_map(&progs[b], map)) return -(at + 2);
+  }
+  return 0;
+}
+// the inputs X, N, ldx, d: at .. at + 3 (d is checked before ldx, which is measured against it).  empty_ok: N == 0 is
+// accepted, and X may then be null (the entry points on a given K^-1 or adjoint); otherwise N >= 1 (those on a factor)
+static inline int g3h_args_inputs(const void* X, int64_t N, int64_t ldx, int d, int at, bool empty_ok) {
+  if (empty_ok ? (!X && N > 0) : !X) return -at;
+  if (empty_ok ? N < 0 : N <= 0) return -(at + 1);
+  if (d < 1 || d > G3_MAXCOLS) return -(at + 3);
+  if (ldx < d) return -(at + 2);
+  return 0;
+}
+// the factor as g3_gp_factor(_batched) left it: L, [N,] ldl, [kstride,] invd, a from `at` on; es = the element size.  kstride
+// null: one member; n_here: N is an argument of this group, between L and ldl (g3_gp_loo*), and is checked in its place
+static inline int g3h_args_factor(const void* L, int64_t N, bool n_here, int64_t ldl, const int64_t* kstride, const void* invd,
+                                  const void* a, size_t es, int at) {
+  const int64_t Np = g3h_roundup(N, G3H_LB), al = 16 / (int64_t)es;
+  if (!L) return -at;
+  if (n_here && N <= 0) return -(at + 1);
+  at += n_here ? 2 : 1;
+  if (ldl < Np || ldl % al) return -at;
+  if (kstride && (*kstride < Np * ldl || *kstride % al)) return -(at + 1);
+  at += kstride ? 2 : 1;
+  if (!invd) return -at;
+  if (!a) return -(at + 1);
+  return 0;
+}
+// a square output of the padded size with its leading dimension: at, at + 1
+static inline int g3h_args_padded_out(const void* P, int64_t ld, int64_t N, size_t es, int at) {
+  if (!P) return -at;
+  if (ld < g3h_roundup(N, G3H_LB) || ld % (16 / (int64_t)es)) return -(at + 1);
+  return 0;
+}
+// a *_batched_fields entry point's status from its whole-programs body's: lo .. -4 name arguments three places further there
+static inline int g3h_fields_status(int rc, int lo) { return (rc <= -4 && rc >= lo) ? rc - 3 : rc; }

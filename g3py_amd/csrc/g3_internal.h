@@ -114,7 +114,6 @@ struct g3_dev_guard {
 };
 #define G3_MAX_DEVICES 64   // per-device caches of function attributes
 
-#define G3_MAX_BATCH 4096
 static inline int g3_nbatch(const g3_ctx* ctx) { return ctx->batch > 1 ? ctx->batch : 1; }
 // element stride between batch members for an operand at p (0 outside batch mode)
 static inline int64_t g3_bstride_of(const g3_ctx* ctx, const void* p) {
@@ -272,11 +271,14 @@ hipFunction_t g3i_grad_jit_function(g3_ctx* ctx, const g3_kernel_prog* prog_host
 int g3i_gram_grad_batched(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const g3_grad_map* map, const void* X, int64_t N,
                           int64_t ldx, int d, g3_dtype dt, const void* G, int64_t ldg, int64_t gstride, const void* alpha,
                           int64_t astride, double* out_host, int64_t row0 = 0, int64_t nrows = -1);
-// 0 = every slot of `map` lies inside [0, nslots) for prog's leaves (the gradient entry points' check of their map argument)
-int g3i_check_map(const g3_kernel_prog* prog, const g3_grad_map* map);
-// bytes at the head of the context's workspace that g3i_gram_grad_batched may use for `batch` members (partial sums,
-// outputs, member programs): a weight matrix kept in the workspace across that call starts behind them
-size_t g3i_gram_grad_head(int batch);
+// g3i_gram_grad_batched may use the head of the context's workspace (g3_grad.hip::gram_grad_head) for `batch` members: what a
+// caller keeps there across that call starts behind it.  The workspace grown to head + bytes, *behind = where those start
+int g3i_reserve_behind_grad(g3_ctx* ctx, int batch, size_t bytes, char** behind);
+// grid of a pass over the lower triangle (n >= 1) by workgroups of 256 columns, rows dealt over grid.y: enough to fill the chip
+static inline dim3 g3_tril_rows_grid(int64_t n, unsigned members = 1) {
+  const int64_t gx = (n + 255) / 256, gy = 16384 / gx;
+  return dim3((unsigned)gx, (unsigned)(gy < 1 ? 1 : (gy > n ? n : gy)), members);
+}
 int g3i_rows_dot_ss_batched(g3_ctx* ctx, const void* V, int64_t m, int64_t n, int64_t ld, const void* a, g3_dtype dt, void* dot,
                             void* ss, int batch, int64_t vstride, int64_t astride, int64_t ostride);
 // rows_dot_ss over the upper triangle of a square Y (npad x npad): rows [0, n) from their diagonal on, rows [n, npad) get 0
@@ -314,6 +316,10 @@ int g3i_gram_jit(g3_ctx* ctx, const g3_kernel_prog* prog_host, const g3_kernel_p
 // C == nullptr: Y = L^-T alone, the K^-1 product is not run
 int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* invd, g3_dtype dt, void* Y,
               int64_t ldy, void* C, int64_t ldc);
+// that sweep for the `batch` members of one factorisation (g3_gp_grad.hip; batch > 1: batch mode, members kstride apart), every
+// member's pivot flag cleared, recorded as one profiler region `tag` of `flops`
+int g3i_kinv_sweep(g3_ctx* ctx, int batch, const void* L, int64_t np, int64_t ldl, int64_t kstride, const void* invd, g3_dtype dt,
+                   void* Y, int64_t ldy, void* Kinv, int64_t ldc, int tag, double flops);
 
 // ---- the members of a chain (MemberProgs, g3_host.h) as the batched entry points use them
 // Every member must be a valid program of ONE structure (whole programs), or the template and member 0 valid (template form:
@@ -337,9 +343,9 @@ struct g3_dev_members {
 int g3i_upload_members(g3_ctx* ctx, const MemberProgs& mp, int batch, size_t stat_bytes, size_t tail_bytes, g3_dev_members* out);
 
 // The *_batched_fields entry points: the template form's own argument checks, then `call(members)` -- the implementation the
-// whole-programs entry point shares, whose checks number their arguments as that entry point does: the codes lo .. -4 name
-// arguments that sit three places further in the _fields signature.  check_batch: batch is refused here, before the fields
-// (g3_gp_factor_batched_fields leaves it to the shared checks, after them).
+// whole-programs entry point shares, whose checks number their arguments as that entry point does (g3h_fields_status maps
+// the codes lo .. -4).  check_batch: batch is refused here, before the fields (g3_gp_factor_batched_fields leaves it to the
+// shared checks, after them).
 template <typename F>
 static inline int g3i_fields_call(const g3_kernel_prog* tmpl, int batch, bool check_batch, const double* fields,
                                   const int32_t* offsets, int nfield, int lo, F&& call) {
@@ -354,6 +360,5 @@ static inline int g3i_fields_call(const g3_kernel_prog* tmpl, int batch, bool ch
   mp.fields = fields;
   mp.offs = offsets;
   mp.nfield = nfield;
-  const int rc = call(mp);
-  return (rc <= -4 && rc >= lo) ? rc - 3 : rc;
+  return g3h_fields_status(call(mp), lo);
 }

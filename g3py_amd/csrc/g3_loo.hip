@@ -164,13 +164,9 @@ static int loo_small_launch(g3_ctx* ctx, const T* L, int64_t ldl, int64_t lstrid
 static int gp_loo_single(g3_ctx* ctx, const void* L, int64_t N, int64_t ldl, const void* invd, const void* a, g3_dtype dt, void* Y,
                          int64_t ldy, void* alpha, void* kdiag) {
   const int64_t Np = g3_roundup(N, G3_LB);
-  int rc = g3i_reset_info(ctx);
+  int rc = g3i_kinv_sweep(ctx, 1, L, Np, ldl, 0, invd, dt, Y, ldy, nullptr, 0, G3_TAG_TRSM, (double)N * N * N / 3.0);
   if (rc) return rc;
-  int rec = g3i_prof_begin(ctx, G3_TAG_TRSM, (double)N * N * N / 3.0);
-  rc = g3i_potri(ctx, L, Np, ldl, invd, dt, Y, ldy, nullptr, 0);
-  g3i_prof_end(ctx, rec);
-  if (rc) return rc;
-  rec = g3i_prof_begin(ctx, G3_TAG_REDUCE, (double)N * (N + 1));
+  const int rec = g3i_prof_begin(ctx, G3_TAG_REDUCE, (double)N * (N + 1));
   rc = g3i_rows_dot_ss_tri(ctx, Y, N, Np, ldy, a, dt, alpha, kdiag);
   g3i_prof_end(ctx, rec);
   return rc;
@@ -181,14 +177,9 @@ extern "C" int g3_gp_loo(g3_ctx* ctx, const void* L_dev, int64_t N, int64_t ldl,
   if (!ctx) return -1;
   g3_dev_guard _dg(ctx);
   if (dt != G3_F64 && dt != G3_F32) return -7;       // (first: the size checks below need the element size)
-  if (!L_dev) return -2;
-  if (N <= 0) return -3;
-  const int64_t Np = g3_roundup(N, G3_LB), al = 16 / (int64_t)g3_esize(dt);
-  if (ldl < Np || ldl % al) return -4;
-  if (!invd_dev) return -5;
-  if (!a_dev) return -6;
-  if (!Y_dev) return -8;
-  if (ldy < Np || ldy % al) return -9;
+  int rc = g3h_args_factor(L_dev, N, true, ldl, nullptr, invd_dev, a_dev, g3_esize(dt), 2);
+  if (!rc) rc = g3h_args_padded_out(Y_dev, ldy, N, g3_esize(dt), 8);
+  if (rc) return rc;
   if (!alpha_dev) return -10;
   if (!kdiag_dev) return -11;
   return gp_loo_single(ctx, L_dev, N, ldl, invd_dev, a_dev, dt, Y_dev, ldy, alpha_dev, kdiag_dev);
@@ -201,14 +192,9 @@ extern "C" int g3_gp_loo_batched(g3_ctx* ctx, int batch, const void* L_dev, int6
   g3_dev_guard _dg(ctx);
   if (dt != G3_F64 && dt != G3_F32) return -9;       // (first: the size checks below need the element size)
   if (batch < 1 || batch > G3_MAX_BATCH) return -2;
-  if (!L_dev) return -3;
-  if (N <= 0) return -4;
   const size_t es = g3_esize(dt);
-  const int64_t Np = g3_roundup(N, G3_LB), al = 16 / (int64_t)es;
-  if (ldl < Np || ldl % al) return -5;
-  if (kstride < Np * ldl || kstride % al) return -6;
-  if (!invd_dev) return -7;
-  if (!a_dev) return -8;
+  const int64_t Np = g3_roundup(N, G3_LB);
+  if (const int bad = g3h_args_factor(L_dev, N, true, ldl, &kstride, invd_dev, a_dev, es, 3)) return bad;
   if (Np > 2 * G3_LB && !Y_dev) return -10;          // one workspace for the members that take the single path
   if (!alpha_dev) return -11;
   if (!kdiag_dev) return -12;

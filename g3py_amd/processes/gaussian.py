@@ -1,4 +1,6 @@
 """GaussianProcess / WarpedGaussianProcess (g3py/processes/gaussian.py:18-260) on the HIP path."""
+from types import SimpleNamespace
+
 import numpy as np
 from scipy import stats
 
@@ -98,6 +100,46 @@ class _Refs(dict):
         return _Ref(name)
 
 
+class _ScoreChain:
+    """The block loop of logp_chain, dlogp_chain, loo_chain and dloo_chain: `with _ScoreChain(...) as sc: for blk in sc:`.
+    X is uploaded once, the chain workspace sc.ws holds sc.batch members (None: what fits in 4 GB -- three matrices per
+    member with the K^-1 workspaces of `grad`, else one); every block is factored in ONE batched sweep before the caller
+    gets it, with blk.ok the rows that do NOT take the constant -1e30 branch (gaussian.py:234-237; st[:, 2] counts the
+    factor's non-finite entries).  Leaving the `with`, whether the loop ended or raised, frees X and what sc.alloc gave."""
+
+    def __init__(self, proc, chain, batch, grad=False):
+        self.proc, self.chain = proc, chain
+        self.X, self.y, self.N, self.d, self.Np, self.kstride, self.batch, self.Xd, self.ws = proc._chain_setup(
+            len(chain), batch, lambda Np, kstride: int(4e9 // ((3 if grad else 1) * kstride * proc.dtype.itemsize)), grad=grad)
+        self.factor = (self.Xd, self.N, self.d, self.ws['K'], self.kstride, self.ws['W'], self.ws['a'])    # as the device takes it
+        self._bufs = [self.Xd]
+
+    def alloc(self, rows, cols):
+        self._bufs.append(self.proc.device.alloc(rows, cols, self.proc.dtype))
+        return self._bufs[-1]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for buf in self._bufs:      # not left to the garbage collector: a sampler evaluates chain after chain
+            buf.free()
+
+    def __iter__(self):
+        p, n_rows = self.proc, len(self.chain)
+        for lo in range(0, n_rows, self.batch):
+            hi = min(lo + self.batch, n_rows)
+            B = hi - lo
+            # the whole block at once on the host: values, programs (one template + the hyper values that differ per
+            # row), warped observations and the mean -- O(B) NumPy passes, no per-row Python
+            values, logjac = p._values_rows(self.chain[lo:hi])
+            members = p._chain_members(p.f_kernel_noise, values, self.d, B)
+            delta, det_m, bad = p._chain_delta_or_bad(values, self.X, self.y, B)
+            st = p._chain_factor_block(members, delta, *self.factor)
+            yield SimpleNamespace(lo=lo, hi=hi, B=B, values=values, logjac=logjac, members=members, delta=delta, det_m=det_m,
+                                  bad=bad, st=st, ok=~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0))
+
+
 class FactorLikelihood:
     """What every elliptical process with a density of the Cholesky factor's two scalars shares -- logp, its gradient and
     their forms over the rows of a chain: mixed into GaussianProcess and StudentTProcess, which supply `_density` and
@@ -178,12 +220,7 @@ class FactorLikelihood:
         if c.get('grad') is None:
             prog = self._prog(self.f_kernel_noise, values, d)
             gmap = dev.grad_layout(prog)
-            ws = self._workspace                 # K^-1 workspaces live with the factor workspace (same data set)
-            if 'Y' not in ws:                    # (loo shares Y: scratch in both)
-                ws['Y'] = dev.alloc(Np, Np, self.dtype)
-            if 'Kinv' not in ws:
-                ws['Kinv'], ws['alpha'] = dev.alloc(Np, Np, self.dtype), dev.alloc(1, Np, self.dtype)
-            Y, Kinv, alpha = ws['Y'], ws['Kinv'], ws['alpha']
+            Y, Kinv, alpha, _ = self._kinv_workspace(Np)
             ad = c['ad']
             if s != 1.0:      # G = s alpha alpha^T - K^-1: hand the device sqrt(s) a, it returns sqrt(s) alpha
                 ad = dev.upload((dev.download(c['ad']) * np.sqrt(s)).astype(self.dtype))
@@ -193,11 +230,28 @@ class FactorLikelihood:
         g = c['grad']
         self._chain_rule(values, c['X'], c['y'], nat, g['prog'], g['gmap'], g['slots'], g['alpha'], d)
 
+    def _zero_gradient(self, B=None):
+        """a natural-space gradient of zeros: {name: v.shape} for one row of values, {name: (B, *v.shape)} for a chain block"""
+        lead = () if B is None else (B,)
+        return {v.name: np.zeros(lead + tuple(v.shape)) for v in self.model.vars}
+
+    def _kinv_workspace(self, Np, kinv=True, vec=None):
+        """(Y, Kinv, alpha, vec): the device buffers of dlogp, loo and dloo, kept with the factor workspace (same data set)
+        and created at first need.  Y is scratch in all three and shared; kinv=False does not create Kinv and alpha; vec
+        names the caller's own two-row vector ('loo': alpha, kdiag; 'dloo': kdiag, u)."""
+        dev, ws = self.device, self._workspace
+        if 'Y' not in ws:
+            ws['Y'] = dev.alloc(Np, Np, self.dtype)
+        if kinv and 'Kinv' not in ws:
+            ws['Kinv'], ws['alpha'] = dev.alloc(Np, Np, self.dtype), dev.alloc(1, Np, self.dtype)
+        if vec is not None and vec not in ws:
+            ws[vec] = dev.alloc(2, Np, self.dtype)
+        return ws['Y'], ws.get('Kinv'), ws.get('alpha'), ws.get(vec)
+
     def _potential_gradient(self, values, B=None):
         """the natural-space gradient every evaluation starts from: the L1 / L2 potentials' (hypers/__init__.py:97-109),
         zeros elsewhere -- {name: v.shape} for one row of values, {name: (B, *v.shape)} for a chain block"""
-        lead = () if B is None else (B,)
-        nat = {v.name: np.zeros(lead + tuple(v.shape)) for v in self.model.vars}
+        nat = self._zero_gradient(B)
         for _, reg, c, sel in self.model.potentials:
             for h in sel:
                 hv = np.asarray(values[h.name], dtype=np.float64)
@@ -287,7 +341,7 @@ class FactorLikelihood:
         prog = self._prog(self.f_kernel_noise, values, d)
         gmap = dev.grad_layout(prog)
         slots = dev.gram_vjp(prog, gmap, c['Xd'], N, d, Kb)
-        nat = {v.name: np.zeros(tuple(v.shape)) for v in self.model.vars}
+        nat = self._zero_gradient()
         self._kernel_slots(nat, prog, gmap, slots, d)
         return self._flat_gradient(values, nat)
 
@@ -398,33 +452,24 @@ class FactorLikelihood:
                 out[i] = self.dlogp(chain[i], array=True)
             return out
         dev = self.device
-        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
-            n_rows, batch, lambda Np, kstride: int(4e9 // (3 * kstride * self.dtype.itemsize)), grad=True)
-        K, Y, Ki, W, a, al = ws['K'], ws['Y'], ws['Ki'], ws['W'], ws['a'], ws['al']
-        for lo in range(0, n_rows, batch):
-            hi = min(lo + batch, n_rows)
-            B = hi - lo
-            # the block's host side in NumPy passes over all rows (as logp_chain): values, programs as template + fields,
-            # warped observations, mean; the device then does factor, K^-1, alpha and the kernel-parameter sums of every
-            # member in batched launches, and the chain rule below is array arithmetic over the rows
-            values_b, _ = self._values_rows(chain[lo:hi])
-            tmpl, offs, fields = members = self._chain_members(self.f_kernel_noise, values_b, d, B)
-            delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
-            st = self._chain_factor_block(members, delta, Xd, N, d, K, kstride, W, a)
-            gmap = dev.grad_layout(tmpl)
-            ok = ~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0)
-            nat = self._potential_gradient(values_b, B)
-            s = self._dlogp_scale(self._nu(values_b, B), st[:, 1], N, nat, ok)
-            if s is not None:     # G = s alpha alpha^T - K^-1: the device gets sqrt(s) a and returns sqrt(s) alpha
-                with np.errstate(all='ignore'):
-                    rs = np.where(ok, np.sqrt(s), 1.0)
-                dev.copy_in(a, (dev.download(a, B, Np) * rs[:, None].astype(self.dtype)).astype(self.dtype))
-            slots = dev.gp_dlogp_batched_fields(tmpl, offs, fields, gmap, Xd, N, d, K, kstride, W, a, Y, Ki, al)
-            alphas = dev.download(al, B, N).astype(np.float64)
-            if s is not None:
-                alphas = alphas * rs[:, None]
-            self._chain_rule(values_b, X, y, nat, tmpl, gmap, slots, alphas, d, ok)
-            out[lo:hi] = self._flat_gradient(values_b, nat, B)
+        with _ScoreChain(self, chain, batch, grad=True) as sc:
+            N, ws, a = sc.N, sc.ws, sc.ws['a']
+            for blk in sc:
+                # K^-1, alpha and the kernel-parameter sums of every member in batched launches; the chain rule is array arithmetic
+                B, values_b, ok = blk.B, blk.values, blk.ok
+                gmap = dev.grad_layout(blk.members[0])
+                nat = self._potential_gradient(values_b, B)
+                s = self._dlogp_scale(self._nu(values_b, B), blk.st[:, 1], N, nat, ok)
+                if s is not None:     # G = s alpha alpha^T - K^-1: the device gets sqrt(s) a and returns sqrt(s) alpha
+                    with np.errstate(all='ignore'):
+                        rs = np.where(ok, np.sqrt(s), 1.0)
+                    dev.copy_in(a, (dev.download(a, B, sc.Np) * rs[:, None].astype(self.dtype)).astype(self.dtype))
+                slots = dev.gp_dlogp_batched_fields(*blk.members, gmap, *sc.factor, ws['Y'], ws['Ki'], ws['al'])
+                alphas = dev.download(ws['al'], B, N).astype(np.float64)
+                if s is not None:
+                    alphas = alphas * rs[:, None]
+                self._chain_rule(values_b, sc.X, sc.y, nat, blk.members[0], gmap, slots, alphas, sc.d, ok)
+                out[blk.lo:blk.hi] = self._flat_gradient(values_b, nat, B)
         return out
 
     # ---- many hyper-parameter vectors on the same observations (stochastic.py:515-520)
@@ -442,22 +487,13 @@ class FactorLikelihood:
             if n_rows:                      # the free variables' terms only (th_logp with prior=True): no device work
                 out[:] = self._values_rows(chain)[1].astype(self.dtype)
             return out
-        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
-            n_rows, batch, lambda Np, kstride: int(4e9 // (kstride * self.dtype.itemsize)))
-        K, W, a = ws['K'], ws['W'], ws['a']
-        for lo in range(0, n_rows, batch):
-            hi = min(lo + batch, n_rows)
-            B = hi - lo
-            # the whole block at once on the host: values, programs (one template + the hyper values that differ per
-            # row), warped observations and the mean -- O(B) NumPy passes, no per-row Python
-            values_b, logjac = self._values_rows(chain[lo:hi])
-            delta, det_m, bad = self._chain_delta_or_bad(values_b, X, y, B)
-            st = self._chain_factor_block(self._chain_members(self.f_kernel_noise, values_b, d, B), delta, Xd, N, d, K, kstride, W, a)
-            with np.errstate(all='ignore'):
-                lp = logjac.astype(self.dtype) + np.asarray(
-                    self._density(st[:, 0], st[:, 1], det_m, N, self._nu(values_b, B)), dtype=self.dtype)
-            bad |= ~np.isfinite(st[:, 0]) | (st[:, 2] > 0)                                # gaussian.py:237
-            out[lo:hi] = np.where(bad, logjac.astype(self.dtype) + t(SENTINEL), lp)
+        with _ScoreChain(self, chain, batch) as sc:
+            for blk in sc:
+                logjac, st = blk.logjac.astype(self.dtype), blk.st
+                with np.errstate(all='ignore'):
+                    dens = self._density(st[:, 0], st[:, 1], blk.det_m, sc.N, self._nu(blk.values, blk.B))
+                    lp = logjac + np.asarray(dens, dtype=self.dtype)
+                out[blk.lo:blk.hi] = np.where(blk.ok, lp, logjac + t(SENTINEL))
         return out
 
 
@@ -649,13 +685,9 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
         const = not (np.all(np.isfinite(c['delta'])) and np.all(np.isfinite(c['det_m'])))     # gaussian.py:234-235
         st = self._solve(c, values, 'post' if const else 'logp')
         if c.get('loo') is None:
-            N, Np, ws = c['N'], c['Np'], self._workspace
-            if 'Y' not in ws:                    # (dlogp's Y: scratch in both)
-                ws['Y'] = dev.alloc(Np, Np, self.dtype)
-            if 'loo' not in ws:
-                ws['loo'] = dev.alloc(2, Np, self.dtype)         # alpha, kdiag
-            vec = ws['loo']
-            dev.gp_loo(N, c['Kd'], c['Wd'], c['ad'], ws['Y'], vec, dev.wrap(vec.offset(1), 1, Np, Np, self.dtype, keep=vec))
+            N, Np = c['N'], c['Np']
+            Y, _, _, vec = self._kinv_workspace(Np, kinv=False, vec='loo')      # (dlogp's Y: scratch in both)
+            dev.gp_loo(N, c['Kd'], c['Wd'], c['ad'], Y, vec, dev.wrap(vec.offset(1), 1, Np, Np, self.dtype, keep=vec))
             c['loo'] = dev.download(vec, 2, N)
         alpha, kdiag = c['loo']
         out = loo_assemble(alpha, kdiag, c['z'], self.f_mapping, values, y=c['y'], dtype=self.dtype,
@@ -680,30 +712,19 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
         if n_rows == 0:
             return out
         dev = self.device
-        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
-            n_rows, batch, lambda Np, kstride: int(4e9 // (kstride * self.dtype.itemsize)))
-        K, W, a = ws['K'], ws['W'], ws['a']
-        vec = dev.alloc(2 * batch, Np, self.dtype)               # a block's alpha rows, then its kdiag rows: one download
-        Y = dev.alloc(Np, Np, self.dtype) if Np > 2 * _lib.G3_PAD else None
-        try:
-            for lo in range(0, n_rows, batch):
-                hi = min(lo + batch, n_rows)
-                B = hi - lo
-                values_b, _ = self._values_rows(chain[lo:hi])
-                delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
-                st = self._chain_factor_block(self._chain_members(self.f_kernel_noise, values_b, d, B), delta, Xd, N, d, K,
-                                              kstride, W, a)
-                dev.gp_loo_batched(B, N, K, kstride, W, a, Y, vec, dev.wrap(vec.offset(B), B, Np, Np, self.dtype, keep=vec))
+        with _ScoreChain(self, chain, batch) as sc:
+            y, N, Np, ws = sc.y, sc.N, sc.Np, sc.ws
+            vec = sc.alloc(2 * sc.batch, Np)                     # a block's alpha rows, then its kdiag rows: one download
+            Y = sc.alloc(Np, Np) if Np > 2 * _lib.G3_PAD else None
+            for blk in sc:
+                B, values_b = blk.B, blk.values
+                kd = dev.wrap(vec.offset(B), B, Np, Np, self.dtype, keep=vec)
+                dev.gp_loo_batched(B, N, ws['K'], sc.kstride, ws['W'], ws['a'], Y, vec, kd)
                 both = dev.download(dev.wrap(vec.ptr, 2 * B, Np, Np, self.dtype, keep=vec), 2 * B, N)
                 with np.errstate(all='ignore'):
                     z = np.asarray(self.f_mapping.inv_rows(y, values_b, B), dtype=self.dtype)
                 lp = loo_assemble(both[:B], both[B:], z, self.f_mapping, values_b, y=y, dtype=self.dtype)['logpredictive']
-                bad |= ~np.isfinite(st[:, 0]) | (st[:, 2] > 0)                                # gaussian.py:237
-                out[lo:hi] = np.where(bad, t(SENTINEL), lp)
-        finally:
-            for buf in (vec, Y, Xd):
-                if buf is not None:
-                    buf.free()
+                out[blk.lo:blk.hi] = np.where(blk.ok, lp, t(SENTINEL))
         return out
 
     def dloo(self, params=None, inputs=None, outputs=None):
@@ -719,7 +740,7 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
         params, _, inputs, outputs, _ = self._call_defaults(params, None, inputs, outputs, False, False)
         dev = self.device
         values, _ = self._values(params)
-        nat = {v.name: np.zeros(tuple(v.shape)) for v in self.model.vars}
+        nat = self._zero_gradient()
         c = self._factor(values, inputs, outputs)
         if not (np.all(np.isfinite(c['delta'])) and np.all(np.isfinite(c['det_m']))):          # gaussian.py:234-235
             return self._flat_gradient(values, nat)
@@ -731,15 +752,8 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
         if g is None or g['stats'] is not st:        # (kept with the factorisation it belongs to)
             prog = self._prog(self.f_kernel_noise, values, d)
             gmap = dev.grad_layout(prog)
-            ws = self._workspace
-            if 'Y' not in ws:                        # (Y, Kinv and alpha: dlogp's, scratch in both)
-                ws['Y'] = dev.alloc(Np, Np, self.dtype)
-            if 'Kinv' not in ws:
-                ws['Kinv'], ws['alpha'] = dev.alloc(Np, Np, self.dtype), dev.alloc(1, Np, self.dtype)
-            if 'dloo' not in ws:
-                ws['dloo'] = dev.alloc(2, Np, self.dtype)        # kdiag, u
-            vec = ws['dloo']
-            slots = dev.gp_dloo(prog, gmap, c['Xd'], N, d, c['Kd'], c['Wd'], c['ad'], ws['Y'], ws['Kinv'], ws['alpha'], vec,
+            Y, Kinv, alpha, vec = self._kinv_workspace(Np, vec='dloo')       # (Y, Kinv and alpha: dlogp's, scratch in both)
+            slots = dev.gp_dloo(prog, gmap, c['Xd'], N, d, c['Kd'], c['Wd'], c['ad'], Y, Kinv, alpha, vec,
                                 dev.wrap(vec.offset(1), 1, Np, Np, self.dtype, keep=vec))
             g = c['dloo'] = dict(stats=st, prog=prog, gmap=gmap, slots=slots, u=dev.download(vec, 2, N)[1].astype(np.float64))
         self._chain_rule(values, c['X'], c['y'], nat, g['prog'], g['gmap'], g['slots'], g['u'], d)
@@ -758,28 +772,18 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
         if n_rows == 0:
             return out
         dev = self.device
-        X, y, N, d, Np, kstride, batch, Xd, ws = self._chain_setup(
-            n_rows, batch, lambda Np, kstride: int(4e9 // (3 * kstride * self.dtype.itemsize)), grad=True)
-        K, Y, Ki, W, a, al = ws['K'], ws['Y'], ws['Ki'], ws['W'], ws['a'], ws['al']
-        vec = dev.alloc(2 * batch, Np, self.dtype)               # a block's kdiag rows, then its u rows
-        try:
-            for lo in range(0, n_rows, batch):
-                hi = min(lo + batch, n_rows)
-                B = hi - lo
-                values_b, _ = self._values_rows(chain[lo:hi])
-                tmpl, offs, fields = members = self._chain_members(self.f_kernel_noise, values_b, d, B)
-                delta, _, bad = self._chain_delta_or_bad(values_b, X, y, B)
-                st = self._chain_factor_block(members, delta, Xd, N, d, K, kstride, W, a)
+        with _ScoreChain(self, chain, batch, grad=True) as sc:
+            Np, ws = sc.Np, sc.ws
+            vec = sc.alloc(2 * sc.batch, Np)                     # a block's kdiag rows, then its u rows
+            for blk in sc:
+                B, tmpl = blk.B, blk.members[0]
                 gmap = dev.grad_layout(tmpl)
-                ok = ~bad & np.isfinite(st[:, 0]) & (st[:, 2] == 0)                           # gaussian.py:234-237
                 ud = dev.wrap(vec.offset(B), B, Np, Np, self.dtype, keep=vec)
-                slots = dev.gp_dloo_batched_fields(tmpl, offs, fields, gmap, Xd, N, d, K, kstride, W, a, Y, Ki, al, vec, ud)
-                nat = {v.name: np.zeros((B,) + tuple(v.shape)) for v in self.model.vars}
-                self._chain_rule(values_b, X, y, nat, tmpl, gmap, slots, dev.download(ud, B, N).astype(np.float64), d, ok)
-                out[lo:hi] = self._flat_gradient(values_b, nat, B)
-        finally:
-            for buf in (vec, Xd):
-                buf.free()
+                slots = dev.gp_dloo_batched_fields(*blk.members, gmap, *sc.factor, ws['Y'], ws['Ki'], ws['al'], vec, ud)
+                nat = self._zero_gradient(B)
+                u = dev.download(ud, B, sc.N).astype(np.float64)
+                self._chain_rule(blk.values, sc.X, sc.y, nat, tmpl, gmap, slots, u, sc.d, blk.ok)
+                out[blk.lo:blk.hi] = self._flat_gradient(blk.values, nat, B)
         return out
 
     # ---- quantiles and draws (gaussian.py:56-97)

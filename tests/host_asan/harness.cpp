@@ -3,7 +3,8 @@
 // table / schedule builder is driven over the shapes the library produces (and some it never should) and its output
 // is checked the way the device consumes it: the tile lookup of the GEMM kernel, the op list of the stripe solve, the
 // chunking of the multi-GPU staircase and the segment lists of its steps, the recursion's split point, the panel-width ladder, panel boundaries, the fast-path matcher, the program ring, the jitter schedule, the layout
-// of the batched entry points' device buffer and the host expansion of a chain member.
+// of the batched entry points' device buffer, the host expansion of a chain member and the argument checks of the entry
+// points that run on a finished factor.
 // TEST INFRASTRUCTURE: never linked into the product.
 #include <math.h>
 #include <stdio.h>
@@ -535,6 +536,221 @@ static void test_member_layout() {
     }
 }
 
+// The argument checks of the nine entry points that run on a finished factor or on K^-1, composed from g3_host.h's group
+// functions exactly as the entry points compose them (g3_grad.hip, g3_gp_grad.hip, g3_loo.hip): every status the GPU tests
+// assert (test_gpu_dloo.py, test_gpu_loo.py, test_gpu_kernels.py), and per entry point two collisions -- two bad arguments at
+// once -- with the status that wins.  The lower number wins except where the entry point has always tested out of order.
+struct EntryArgs {
+  const g3_kernel_prog* prog;     // one program, or the chain's programs
+  int batch = 1;
+  const g3_grad_map* map;
+  const void *X, *L, *invd, *a, *Y, *Kinv, *alpha, *kdiag, *u, *G, *out;
+  int64_t N = 100, ldx = 2, ldl = 128, kstride = 256 * 128, ldy = 128, ldc = 128, ldg = 128, row0 = 0, nrows = 100;
+  int d = 2, dt = G3_F64;
+  size_t es() const { return dt == G3_F64 ? 8 : 4; }
+  bool dt_ok() const { return dt == G3_F64 || dt == G3_F32; }
+};
+static int args_gram_grad_head(const EntryArgs& a) {
+  const int rc = g3h_args_prog(a.prog, a.map, 2);
+  return rc ? rc : g3h_args_inputs(a.X, a.N, a.ldx, a.d, 4, true);
+}
+static int args_gram_grad(const EntryArgs& a) {
+  if (const int rc = args_gram_grad_head(a)) return rc;
+  if (!a.G && a.N > 0) return -9;
+  if (a.ldg < a.N) return -10;
+  if (!a.alpha && a.N > 0) return -11;
+  return a.out ? 0 : -12;
+}
+static int args_gram_grad_rows(const EntryArgs& a) {
+  if (const int rc = args_gram_grad_head(a)) return rc;
+  if (a.row0 < 0 || a.row0 % 64) return -9;
+  if (a.nrows < 0 || a.row0 + a.nrows > a.N) return -10;
+  if (!a.G && a.nrows > 0) return -11;
+  if (a.ldg < a.row0 + a.nrows) return -12;
+  if (!a.alpha && a.N > 0) return -13;
+  return a.out ? 0 : -14;
+}
+static int args_gram_vjp(const EntryArgs& a) {       // (G, ldg: Kbar and its leading dimension)
+  if (const int rc = args_gram_grad_head(a)) return rc;
+  if (!a.dt_ok()) return -8;
+  if (!a.G && a.N > 0) return -9;
+  if (a.ldg < a.N) return -10;
+  return a.out ? 0 : -11;
+}
+static int args_gp_dlogp(const EntryArgs& a) {
+  int rc = g3h_args_prog(a.prog, a.map, 2);
+  if (!rc) rc = g3h_args_inputs(a.X, a.N, a.ldx, a.d, 4, false);
+  if (!rc) rc = g3h_args_factor(a.L, a.N, false, a.ldl, nullptr, a.invd, a.a, a.es(), 8);
+  if (!rc) rc = g3h_args_padded_out(a.Y, a.ldy, a.N, a.es(), 13);
+  if (!rc) rc = g3h_args_padded_out(a.Kinv, a.ldc, a.N, a.es(), 15);
+  if (rc) return rc;
+  if (!a.alpha) return -17;
+  return a.out ? 0 : -18;
+}
+static int args_gp_dlogp_batched(const EntryArgs& a) {
+  int rc = g3h_args_progs(a.prog, a.batch, a.map, 2);
+  if (!rc) rc = g3h_args_inputs(a.X, a.N, a.ldx, a.d, 5, false);
+  if (!rc) rc = g3h_args_factor(a.L, a.N, false, a.ldl, &a.kstride, a.invd, a.a, a.es(), 9);
+  if (rc) return rc;
+  if (!a.Y) return -15;
+  if (!a.Kinv) return -16;
+  if (!a.alpha) return -17;
+  return a.out ? 0 : -18;
+}
+static int args_gp_dloo(const EntryArgs& a) {
+  int rc = g3h_args_prog(a.prog, a.map, 2);
+  if (!rc) rc = g3h_args_inputs(a.X, a.N, a.ldx, a.d, 4, false);
+  if (rc) return rc;
+  if (!a.dt_ok()) return -12;
+  rc = g3h_args_factor(a.L, a.N, false, a.ldl, nullptr, a.invd, a.a, a.es(), 8);
+  if (!rc) rc = g3h_args_padded_out(a.Y, a.ldy, a.N, a.es(), 13);
+  if (!rc) rc = g3h_args_padded_out(a.Kinv, a.ldc, a.N, a.es(), 15);
+  if (rc) return rc;
+  if (!a.alpha) return -17;
+  if (!a.kdiag) return -18;
+  if (!a.u) return -19;
+  return a.out ? 0 : -20;
+}
+static int args_gp_dloo_batched(const EntryArgs& a) {       // the whole-programs body of g3_gp_dloo_batched_fields
+  int rc = g3h_args_progs(a.prog, a.batch, a.map, 2);
+  if (!rc) rc = g3h_args_inputs(a.X, a.N, a.ldx, a.d, 5, false);
+  if (rc) return rc;
+  if (!a.dt_ok()) return -14;
+  rc = g3h_args_factor(a.L, a.N, false, a.ldl, &a.kstride, a.invd, a.a, a.es(), 9);
+  if (rc) return rc;
+  if (!a.Y) return -15;
+  if (!a.Kinv) return -16;
+  if (!a.alpha) return -17;
+  if (!a.kdiag) return -18;
+  if (!a.u) return -19;
+  return a.out ? 0 : -20;
+}
+static int args_gp_loo(const EntryArgs& a) {
+  if (!a.dt_ok()) return -7;
+  int rc = g3h_args_factor(a.L, a.N, true, a.ldl, nullptr, a.invd, a.a, a.es(), 2);
+  if (!rc) rc = g3h_args_padded_out(a.Y, a.ldy, a.N, a.es(), 8);
+  if (rc) return rc;
+  if (!a.alpha) return -10;
+  return a.kdiag ? 0 : -11;
+}
+static int args_gp_loo_batched(const EntryArgs& a) {
+  if (!a.dt_ok()) return -9;
+  if (a.batch < 1 || a.batch > G3_MAX_BATCH) return -2;
+  if (const int rc = g3h_args_factor(a.L, a.N, true, a.ldl, &a.kstride, a.invd, a.a, a.es(), 3)) return rc;
+  if (g3h_roundup(a.N, G3H_LB) > 2 * G3H_LB && !a.Y) return -10;
+  if (!a.alpha) return -11;
+  return a.kdiag ? 0 : -12;
+}
+
+static void test_argument_groups() {
+  g3_kernel_prog prog;                    // var * SE(x0, x1) + noise, as the GPU tests' compile_spec(('sum', SE, NOISE), 2)
+  memset(&prog, 0, sizeof(prog));
+  prog.nleaf = 2;
+  prog.nprod = 2;
+  prog.leaf[0].kind = G3_K_SE;
+  prog.leaf[0].ndims = 2;
+  prog.leaf[0].dims[1] = 1;
+  prog.leaf[1].kind = G3_K_NOISE;
+  for (int q = 0; q < 2; ++q) { prog.prod[q].nfac = 1; prog.prod[q].fac[0] = q; prog.prod[q].coef = 1.0; }
+  g3_grad_map map;
+  for (int l = 0; l < G3_MAXLEAF; ++l) map.var[l] = map.alpha[l] = map.rate[l] = map.freq[l] = -1;
+  map.var[0] = 0; map.rate[0] = 1; map.var[1] = 3; map.nslots = 4;
+  CHECK(!g3h_check_map(&prog, &map));
+  g3_grad_map badmap = map;               // a slot outside the output
+  badmap.var[0] = badmap.nslots;
+  g3_kernel_prog badprog = prog;
+  badprog.nprod = G3_MAXPROD + 1;
+  char mem[8];
+  const void* p = mem;                    // never dereferenced: the checks look at pointers, not through them
+  EntryArgs ok;
+  ok.prog = &prog; ok.map = &map;
+  ok.X = ok.L = ok.invd = ok.a = ok.Y = ok.Kinv = ok.alpha = ok.kdiag = ok.u = ok.G = ok.out = p;
+  auto with = [&](auto&& change) { EntryArgs a = ok; change(a); return a; };
+#define ARGS(...) with([&](EntryArgs& a) { __VA_ARGS__; })
+  for (auto f : {args_gram_grad, args_gram_grad_rows, args_gram_vjp, args_gp_dlogp, args_gp_dlogp_batched, args_gp_dloo,
+                 args_gp_dloo_batched, args_gp_loo, args_gp_loo_batched}) {
+    CHECK(f(ok) == 0);
+    CHECK(f(ARGS(a.dt = G3_F32; a.ldl = a.ldy = a.ldc = 132)) == 0);      // rows of 4-byte elements: multiples of 4
+  }
+  // ---- g3_gp_dloo (test_gpu_dloo.py::test_argument_checks)
+  CHECK(args_gp_dloo(ARGS(a.prog = nullptr)) == -2 && args_gp_dloo(ARGS(a.map = nullptr)) == -3);
+  CHECK(args_gp_dloo(ARGS(a.X = nullptr)) == -4 && args_gp_dloo(ARGS(a.N = 0)) == -5 && args_gp_dloo(ARGS(a.ldx = 1)) == -6);
+  CHECK(args_gp_dloo(ARGS(a.d = 0)) == -7 && args_gp_dloo(ARGS(a.L = nullptr)) == -8);
+  CHECK(args_gp_dloo(ARGS(a.N = 129; a.ldy = a.ldc = 256)) == -9);       // ldl below roundup(N, 128)
+  CHECK(args_gp_dloo(ARGS(a.invd = nullptr)) == -10 && args_gp_dloo(ARGS(a.a = nullptr)) == -11 && args_gp_dloo(ARGS(a.dt = 7)) == -12);
+  CHECK(args_gp_dloo(ARGS(a.Y = nullptr)) == -13 && args_gp_dloo(ARGS(a.ldy = 127)) == -14 && args_gp_dloo(ARGS(a.Kinv = nullptr)) == -15);
+  CHECK(args_gp_dloo(ARGS(a.ldc = 127)) == -16 && args_gp_dloo(ARGS(a.alpha = nullptr)) == -17 && args_gp_dloo(ARGS(a.kdiag = nullptr)) == -18);
+  CHECK(args_gp_dloo(ARGS(a.u = nullptr)) == -19 && args_gp_dloo(ARGS(a.out = nullptr)) == -20);
+  CHECK(args_gp_dloo(ARGS(a.map = &badmap)) == -3 && args_gp_dloo(ARGS(a.prog = &badprog)) == -2);
+  CHECK(args_gp_dloo(ARGS(a.prog = &badprog; a.map = nullptr)) == -2);    // collisions
+  CHECK(args_gp_dloo(ARGS(a.dt = 7; a.L = nullptr)) == -12);              // dt is tested before the factor
+  CHECK(args_gp_dloo(ARGS(a.dt = 7; a.d = 0)) == -7);                     // ... and after the inputs
+  CHECK(args_gp_dloo(ARGS(a.ldx = 1; a.d = 0)) == -7);                    // d before ldx, which is measured against it
+  // ---- g3_gp_dloo_batched_fields: the whole-programs body's codes, three places further from -4 on
+  auto many = [&](const EntryArgs& a) { return g3h_fields_status(args_gp_dloo_batched(a), -20); };
+  CHECK(many(ARGS(a.batch = 0)) == -3 && many(ARGS(a.batch = G3_MAX_BATCH + 1)) == -3 && many(ARGS(a.map = nullptr)) == -7);
+  CHECK(many(ARGS(a.X = nullptr)) == -8 && many(ARGS(a.N = 0)) == -9 && many(ARGS(a.ldx = 1)) == -10 && many(ARGS(a.d = 0)) == -11);
+  CHECK(many(ARGS(a.L = nullptr)) == -12 && many(ARGS(a.ldl = 127)) == -13);
+  CHECK(many(ARGS(a.kstride = 127 * 128)) == -14);                         // members would overlap
+  CHECK(many(ARGS(a.invd = nullptr)) == -15 && many(ARGS(a.a = nullptr)) == -16 && many(ARGS(a.dt = 7)) == -17);
+  CHECK(many(ARGS(a.Y = nullptr)) == -18 && many(ARGS(a.Kinv = nullptr)) == -19 && many(ARGS(a.alpha = nullptr)) == -20);
+  CHECK(many(ARGS(a.kdiag = nullptr)) == -21 && many(ARGS(a.u = nullptr)) == -22 && many(ARGS(a.out = nullptr)) == -23);
+  CHECK(g3h_fields_status(-2, -20) == -2 && g3h_fields_status(-3, -20) == -3 && g3h_fields_status(-21, -20) == -21);
+  CHECK(g3h_fields_status(-100, -20) == -100 && g3h_fields_status(0, -20) == 0);      // G3_ERR_*: not argument numbers
+  CHECK(args_gp_dloo_batched(ARGS(a.map = nullptr; a.prog = &badprog)) == -4);        // collisions: the missing map is refused
+  CHECK(args_gp_dloo_batched(ARGS(a.map = &badmap; a.prog = &badprog)) == -2);        // before a member is looked at
+  CHECK(args_gp_dloo_batched(ARGS(a.dt = 7; a.kstride = 1)) == -14);
+  // ---- g3_gp_dlogp, g3_gp_dlogp_batched: the same numbers without dt, kdiag and u
+  CHECK(args_gp_dlogp(ARGS(a.prog = nullptr)) == -2 && args_gp_dlogp(ARGS(a.map = &badmap)) == -3 && args_gp_dlogp(ARGS(a.N = 0)) == -5);
+  CHECK(args_gp_dlogp(ARGS(a.ldl = 127)) == -9 && args_gp_dlogp(ARGS(a.ldy = 127)) == -14 && args_gp_dlogp(ARGS(a.ldc = 127)) == -16);
+  CHECK(args_gp_dlogp(ARGS(a.alpha = nullptr)) == -17 && args_gp_dlogp(ARGS(a.out = nullptr)) == -18);
+  CHECK(args_gp_dlogp(ARGS(a.dt = 7)) == 0);                               // no test of dt: anything but G3_F64 is float
+  CHECK(args_gp_dlogp(ARGS(a.dt = G3_F32; a.ldl = 130)) == -9);            // ... whose rows are multiples of 4 elements
+  CHECK(args_gp_dlogp(ARGS(a.invd = nullptr; a.Y = nullptr)) == -10 && args_gp_dlogp(ARGS(a.Kinv = nullptr; a.ldy = 127)) == -14);
+  CHECK(args_gp_dlogp_batched(ARGS(a.prog = nullptr)) == -2 && args_gp_dlogp_batched(ARGS(a.batch = 0)) == -3);
+  CHECK(args_gp_dlogp_batched(ARGS(a.map = nullptr)) == -4 && args_gp_dlogp_batched(ARGS(a.map = &badmap)) == -4);
+  CHECK(args_gp_dlogp_batched(ARGS(a.kstride = 128 * 128 + 1)) == -11 && args_gp_dlogp_batched(ARGS(a.a = nullptr)) == -13);
+  CHECK(args_gp_dlogp_batched(ARGS(a.Y = nullptr)) == -15 && args_gp_dlogp_batched(ARGS(a.out = nullptr)) == -18);
+  CHECK(args_gp_dlogp_batched(ARGS(a.dt = 7)) == 0);
+  CHECK(args_gp_dlogp_batched(ARGS(a.batch = 0; a.map = nullptr)) == -3 && args_gp_dlogp_batched(ARGS(a.ldl = 127; a.kstride = 1)) == -10);
+  {   // the second member is looked at too
+    g3_kernel_prog two[2] = {prog, badprog};
+    CHECK(args_gp_dlogp_batched(ARGS(a.prog = two; a.batch = 2)) == -2 && args_gp_dlogp_batched(ARGS(a.prog = two; a.batch = 1)) == 0);
+  }
+  // ---- g3_gram_grad, g3_gram_grad_rows, g3_gram_vjp (test_gpu_kernels.py): N == 0 with null pointers is a valid call
+  CHECK(args_gram_grad(ARGS(a.N = 10; a.ldx = 1)) == -6 && args_gram_grad(ARGS(a.N = 10; a.map = &badmap)) == -3);
+  CHECK(args_gram_grad(ARGS(a.N = 0; a.X = a.G = a.alpha = nullptr)) == 0 && args_gram_grad(ARGS(a.X = nullptr)) == -4);
+  CHECK(args_gram_grad(ARGS(a.N = -1)) == -5 && args_gram_grad(ARGS(a.G = nullptr)) == -9 && args_gram_grad(ARGS(a.ldg = 99)) == -10);
+  CHECK(args_gram_grad(ARGS(a.alpha = nullptr)) == -11 && args_gram_grad(ARGS(a.out = nullptr)) == -12 && args_gram_grad(ARGS(a.dt = 7)) == 0);
+  CHECK(args_gram_grad(ARGS(a.N = -1; a.X = nullptr)) == -5 && args_gram_grad(ARGS(a.d = 41; a.G = nullptr)) == -7);
+  CHECK(args_gram_grad_rows(ARGS(a.row0 = 32)) == -9 && args_gram_grad_rows(ARGS(a.row0 = 64; a.nrows = 37)) == -10);
+  CHECK(args_gram_grad_rows(ARGS(a.G = nullptr)) == -11 && args_gram_grad_rows(ARGS(a.ldg = 99)) == -12);
+  CHECK(args_gram_grad_rows(ARGS(a.alpha = nullptr)) == -13 && args_gram_grad_rows(ARGS(a.out = nullptr)) == -14);
+  CHECK(args_gram_grad_rows(ARGS(a.N = 0; a.nrows = 0; a.X = a.G = a.alpha = nullptr)) == 0);
+  CHECK(args_gram_grad_rows(ARGS(a.prog = nullptr; a.row0 = 1)) == -2 && args_gram_grad_rows(ARGS(a.row0 = 1; a.nrows = -1)) == -9);
+  CHECK(args_gram_vjp(ARGS(a.dt = 7)) == -8 && args_gram_vjp(ARGS(a.G = nullptr)) == -9 && args_gram_vjp(ARGS(a.ldg = 99)) == -10);
+  CHECK(args_gram_vjp(ARGS(a.out = nullptr)) == -11 && args_gram_vjp(ARGS(a.N = 0; a.X = a.G = nullptr)) == 0);
+  CHECK(args_gram_vjp(ARGS(a.dt = 7; a.ldx = 1)) == -6 && args_gram_vjp(ARGS(a.dt = 7; a.out = nullptr)) == -8);
+  // ---- g3_gp_loo, g3_gp_loo_batched (test_gpu_loo.py::test_argument_checks): dt first of all, N between L and ldl
+  CHECK(args_gp_loo(ARGS(a.L = nullptr)) == -2 && args_gp_loo(ARGS(a.N = 0)) == -3);
+  CHECK(args_gp_loo(ARGS(a.N = 129; a.ldy = 256)) == -4);                  // ldl below roundup(N, 128)
+  CHECK(args_gp_loo(ARGS(a.invd = nullptr)) == -5 && args_gp_loo(ARGS(a.a = nullptr)) == -6 && args_gp_loo(ARGS(a.dt = 7)) == -7);
+  CHECK(args_gp_loo(ARGS(a.Y = nullptr)) == -8 && args_gp_loo(ARGS(a.ldy = 127)) == -9 && args_gp_loo(ARGS(a.alpha = nullptr)) == -10);
+  CHECK(args_gp_loo(ARGS(a.kdiag = nullptr)) == -11);
+  CHECK(args_gp_loo(ARGS(a.dt = 7; a.L = nullptr)) == -7 && args_gp_loo(ARGS(a.N = 0; a.ldl = 0; a.L = nullptr)) == -2);
+  CHECK(args_gp_loo(ARGS(a.N = 0; a.ldl = 127)) == -3);
+  CHECK(args_gp_loo_batched(ARGS(a.batch = 0; a.Y = nullptr)) == -2 && args_gp_loo_batched(ARGS(a.batch = 4097; a.Y = nullptr)) == -2);
+  CHECK(args_gp_loo_batched(ARGS(a.L = nullptr)) == -3 && args_gp_loo_batched(ARGS(a.N = 0)) == -4 && args_gp_loo_batched(ARGS(a.ldl = 127)) == -5);
+  CHECK(args_gp_loo_batched(ARGS(a.kstride = 127 * 128; a.Y = nullptr)) == -6);      // members would overlap
+  CHECK(args_gp_loo_batched(ARGS(a.invd = nullptr)) == -7 && args_gp_loo_batched(ARGS(a.a = nullptr)) == -8 && args_gp_loo_batched(ARGS(a.dt = 7)) == -9);
+  CHECK(args_gp_loo_batched(ARGS(a.N = 300; a.ldl = 384; a.kstride = 512 * 384; a.Y = nullptr)) == -10);   // N > 256 needs the Y workspace
+  CHECK(args_gp_loo_batched(ARGS(a.N = 300; a.ldl = 384; a.kstride = 512 * 384; a.Y = a.alpha = a.kdiag = nullptr)) == -10);
+  CHECK(args_gp_loo_batched(ARGS(a.Y = nullptr)) == 0);                    // ... and no other
+  CHECK(args_gp_loo_batched(ARGS(a.Y = a.alpha = nullptr)) == -11 && args_gp_loo_batched(ARGS(a.Y = a.kdiag = nullptr)) == -12);
+  CHECK(args_gp_loo_batched(ARGS(a.dt = 7; a.batch = 0)) == -9 && args_gp_loo_batched(ARGS(a.batch = 0; a.L = nullptr)) == -2);
+#undef ARGS
+}
+
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "deal")) {        // "deal P nblk": print the table (the Python twin must deal identically)
     std::vector<int> owner;
@@ -552,6 +768,7 @@ int main(int argc, char** argv) {
   test_match_and_validate();
   test_ring_and_jitter();
   test_member_layout();
+  test_argument_groups();
   if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }
   printf("host_asan ok\n");
   return 0;
