@@ -560,7 +560,7 @@ struct SeGradParams {
   double rate[D];
   double var, alpha;
   // optional periodic term (COS, SIN or SM: kernels.py:466-467, 471-472, 486-487), added to the stationary term or
-  // multiplied with it (mul): f = 2 pi freq, pr = the periodic leaf's rate
+  // multiplied with it (mul): f = freq (periods per unit), pr = the periodic leaf's rate
   double f[D], pr[D];
   double pvar;
   int mul;
@@ -618,7 +618,10 @@ gram_grad_se_kernel(SeGradParams<D> se, const T* __restrict__ X, int64_t N, int6
     if constexpr (PER) {
       for (int e = tid; e < 2 * GG_T * D; e += GG_THREADS) {
         const int side = e / (GG_T * D), q = e - side * (GG_T * D), r = q / D, k = q - r * D;
-        const double th = se.f[k] * (side ? xj_s[r * dp + k] : xi_s[r * dp + k]);
+        // theta modulo 2 pi: the whole periods taken off the exact product freq * x by one fma (g3_kernel_eval.h::trig_theta);
+        // rounded by eps * pi, not by eps * |theta|, which grows with |x| although the sums depend on dx alone
+        const double x = side ? xj_s[r * dp + k] : xi_s[r * dp + k];
+        const double th = (2.0 * GG_PI) * fma(se.f[k], x, -rint(se.f[k] * x));
         double* t = (side ? tj_s : ti_s) + r * TS2 + 2 * k;
         t[0] = cos(th);
         t[1] = sin(th);
@@ -790,7 +793,7 @@ static int match_se_grad(const g3_kernel_prog* p, int d, SeGradParams<D>* out, i
     if (!((kd == G3_K_SE || kd == G3_K_MAT32 || kd == G3_K_MAT52) && (D == 1 || D == 2 || D == 4 || D == 8)) || pl.ndims != D) return -1;
     for (int k = 0; k < D; ++k) {
       if (pl.dims[k] != k) return -1;
-      out->f[k] = 2.0 * GG_PI * pl.freq[k];
+      out->f[k] = pl.freq[k];
       out->pr[k] = pl.rate[k];
     }
     out->pvar = pl.var;

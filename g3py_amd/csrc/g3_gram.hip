@@ -98,20 +98,19 @@ gram_kernel(const g3_kernel_prog* __restrict__ prog, SeParams<T, D> se, const T*
       const g3_leaf& lf = prog->leaf[l];
       const int k = t - toff_s[l];
       const T x = (pnt < gt ? xi_s[pnt * dp + lf.dims[k]] : xj_s[(pnt - gt) * dp + lf.dims[k]]);
-      const T scale = (lf.kind == G3_K_SINC) ? T(2 * G3_PI * G3_PI) : T(2 * G3_PI);
-      const T th = scale * (T)lf.freq[k] * x;
+      const T th = trig_theta((T)lf.freq[k], x);        // modulo 2 pi, from the exact product (g3_kernel_eval.h)
       const T sn = sin(th), cs = cos(th);
       trig_s[pnt * tstride + 2 * t] = cs;
       trig_s[pnt * tstride + 2 * t + 1] = sn;
     }
   }
-  constexpr int FTS = 2 * D + 1;        // fast path: [cos, sin] of 2 pi freq_k x_k per point, odd row stride
+  constexpr int FTS = 2 * D + 1;        // fast path: [cos, sin] of 2 pi freq_k x_k (mod 2 pi) per point, odd row stride
   if constexpr (SE_FAST && PK >= 0) {
     __syncthreads();
     for (int e = tid; e < (gt + GTN) * D; e += 256) {
       const int pnt = e / D, k = e - pnt * D;
       const T x = pnt < gt ? xi_s[pnt * dp + k] : xj_s[(pnt - gt) * dp + k];
-      const T th = se.f[k] * x;
+      const T th = trig_theta(se.f[k], x);                // as the generic path
       trig_s[pnt * FTS + 2 * k] = cos(th);
       trig_s[pnt * FTS + 2 * k + 1] = sin(th);
     }

@@ -199,12 +199,15 @@ g3_gram_jit(const jprog* __restrict__ prog, const T* __restrict__ X1, i64 n1, i6
   }
   if constexpr (JNTRIG > 0) {
     __syncthreads();
-    // [cos, sin] of 2 pi freq x for every (periodic leaf, dimension) pair and the 64 + 128 points of the tile
+    // [cos, sin] of 2 pi freq x for every (periodic leaf, dimension) pair and the 64 + 128 points of the tile; theta modulo
+    // 2 pi, the whole periods taken off the exact product by one fma, as g3_kernel_eval.h::trig_theta (rounded by eps * pi
+    // whatever x is)
     for (int e = tid; e < (GT + GTN) * JNTRIG; e += 256) {
       const int pnt = e / JNTRIG, t = e - pnt * JNTRIG;
       const int l = jtleaf[t], k = jtk[t];
       const T x = pnt < GT ? xi_s[pnt * dp + jtcol[t]] : xj_s[(pnt - GT) * dp + jtcol[t]];
-      const T th = T(2 * G3_PI) * (T)prog->leaf[l].freq[k] * x;
+      const T f = (T)prog->leaf[l].freq[k];
+      const T th = T(2 * G3_PI) * fma(f, x, -rint(f * x));
       trig_s[pnt * tstride + 2 * t] = cos(th);
       trig_s[pnt * tstride + 2 * t + 1] = sin(th);
     }

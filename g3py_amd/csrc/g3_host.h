@@ -511,7 +511,7 @@ template <typename T, int D>
 struct SeParams {
   T w[D];   // ARD_L2 kinds: 0.5 * rate^2 ; OU (ARD_L1): rate
   T var, noise, alpha;
-  // optional second term, a periodic leaf on the same columns (kernels.py:466-487): f = 2 pi freq,
+  // optional second term, a periodic leaf on the same columns (kernels.py:466-487): f = freq (periods per unit),
   // pr = its rate vector (SIN: rate; SM: rate^2 * 2 pi^2; COS: unused)
   T f[D];
   T pr[D];
@@ -575,7 +575,7 @@ static inline int g3h_match_fast(const g3_kernel_prog* p, int d, SeParams<T, D>*
     if (!have || pl.ndims != D) return -1;
     for (int k = 0; k < D; ++k) {
       if (pl.dims[k] != k) return -1;
-      out->f[k] = T(2 * G3H_PI) * (T)pl.freq[k];     // the generic path's  (2 pi * freq) * x
+      out->f[k] = (T)pl.freq[k];                     // in periods per unit: the table reduces freq * x modulo 1 (trig_theta)
       out->pr[k] = pl.kind == G3_K_SM ? (T)pl.rate[k] * (T)pl.rate[k] : (T)pl.rate[k];
     }
     out->pvar = (T)pl.var;

@@ -10,14 +10,29 @@
 #define G3_PI 3.14159265358979323846
 
 // Periodic leaves depend on the pair only through cos / sin of theta_i - theta_j with
-// theta = scale * freq_k * x_k.  When `ti`, `tj` are given they hold, per point,
-// [cos(theta_k), sin(theta_k)] pairs prepared once per tile, and the pair value costs two
-// FMAs per dimension instead of one fp64 cos/sin (the angle-difference identities are exact;
-// the only deviation from the direct formula is the rounding of theta itself).
+// theta = 2 pi freq_k x_k.  When `ti`, `tj` are given they hold, per point, [cos(theta_k), sin(theta_k)]
+// pairs prepared once per tile, and the pair value costs two FMAs per dimension instead of one fp64
+// cos/sin.  The angle-difference identities are exact; the deviation from the direct formula is the
+// rounding of the two thetas.  Formed as a plain product, theta is rounded by eps * |theta|, which
+// grows with |x| although K depends on dx alone: 1e-3 in fp32 for a yearly period on inputs in
+// calendar years, 1e-6 in fp64 on Unix timestamps.  Measuring x from a point of the tile only trades
+// |x| for the tile's extent (64 periods across a tile: 2e-5 in fp32, ten times the direct formula's
+// error on the close pairs a locally periodic kernel lives on).  So the tables take theta modulo
+// 2 pi off the EXACT product, trig_theta below: its error is eps * pi whatever x is.
 // (SINC divides sin(theta_i - theta_j) by dx: the absolute rounding of theta would be amplified
 //  for close points, so SINC keeps the direct formula.)
 __host__ __device__ __forceinline__ bool leaf_has_trig(int kind) {
   return kind == G3_K_COS || kind == G3_K_SIN || kind == G3_K_SM;
+}
+
+// theta = 2 pi freq x modulo 2 pi for a trig-table entry, in [-pi, pi] (to rounding).  The whole periods n come from the
+// rounded product; the fma then takes them off the EXACT product with one rounding, of a fraction of a period
+// (|.| <= 1/2 + eps |n|).  Written so that fusing the first product into something else cannot change it: rint() sits
+// between it and any addition.  A non-finite x gives NaN, as cos / sin of it always did.
+template <typename T>
+__device__ __forceinline__ T trig_theta(T freq, T x) {
+  const T n = rint(freq * x);
+  return T(2 * G3_PI) * fma(freq, x, -n);
 }
 
 // exp(x) for the compile-time fast paths.  Round 3 built an own fp64 exp -- n = rint(x / ln 2), r = x - n ln 2 in two
