@@ -5,7 +5,7 @@
 #include <stdlib.h>
 
 // ----------------------------------------------------------------------------- context
-extern "C" int g3_version(void) { return 104; }
+extern "C" int g3_version(void) { return 105; }
 
 static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out);
 extern "C" int g3_ctx_create(int device, g3_ctx** out) { return ctx_create_impl(device, nullptr, out); }
@@ -913,11 +913,49 @@ int g3i_upload_members(g3_ctx* ctx, const MemberProgs& mp, int batch, size_t sta
 
 // the members' pivot flags of the factorisation just queued -> ctx->h_info (valid once the stream is synchronised), and the
 // device flags cleared for the next call: through g3i_reset_info inside the sweep's batch mode, else all `batch` directly
-static int read_member_flags(g3_ctx* ctx, int batch, bool in_batch_mode) {
-  if (hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+static int read_member_flags(g3_ctx* ctx, int batch, bool in_batch_mode, int* flags_host, int* flags_dev) {
+  if (hipMemcpyAsync(flags_host, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    return G3_ERR_HIP;
+  if (flags_dev && hipMemcpyAsync(flags_dev, ctx->d_info, sizeof(int) * batch, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
     return G3_ERR_HIP;
   if (in_batch_mode) return g3i_reset_info(ctx);
   return hipMemsetAsync(ctx->d_info, 0, sizeof(int) * batch, ctx->stream) != hipSuccess ? G3_ERR_HIP : G3_OK;
+}
+
+int g3i_factor_members(g3_ctx* ctx, int batch, int64_t N, int64_t Np, const void* delta, int64_t ldd, g3_dtype dt, void* K, int64_t ldk,
+                       int64_t kstride, void* invd, void* a, double* dstats, unsigned* coop_ctl, int* flags_host, int* flags_dev) {
+  const int64_t RB = 128, wstride = Np * G3_LB;
+  const size_t es = g3_esize(dt);
+  char* rhs = (char*)K + (size_t)Np * ldk * es;
+  const bool small = Np <= 2 * G3_LB;       // one workgroup per member does the whole evaluation (g3i_small_factor_batched)
+  int rc;
+  const int pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)batch * ((double)N * N * N / 3.0 + (double)N * N));
+  if (small) {
+    rc = g3i_small_factor_batched(ctx, K, ldk, kstride, invd, wstride, delta, ldd, a, Np, dstats, batch, N, Np, dt);
+    g3i_prof_end(ctx, pr);
+    if (!rc) rc = read_member_flags(ctx, batch, false, flags_host, flags_dev);
+  } else if (coop_ctl && Np <= ctx->tune.coop_max_n && batch >= ctx->tune.coop_min_batch) {
+    // long chains of medium members: a group of workgroups per member, the whole batch in ONE launch (g3_chainb.hip): 1.2 -
+    // 1.3x the lock-step sweep below at N <= 512, 1.08x at 768 - 1024; short batches (< ~200 members) stay with the sweep,
+    // whose launches are at least as wide as the batch (profiles/r05_chain_medium.txt)
+    rc = g3i_coop_factor_batched(ctx, K, ldk, kstride, invd, wstride, coop_ctl, batch, Np, dt);
+    g3i_prof_end(ctx, pr);
+    if (!rc) rc = read_member_flags(ctx, batch, false, flags_host, flags_dev);
+  } else {
+    // one sweep factors every member; a member whose pivot fails only stops its own launches
+    g3_batch_scope mode(ctx, batch, kstride, wstride, invd, (size_t)batch * wstride * es);
+    rc = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, RB);
+    g3i_prof_end(ctx, pr);
+    if (!rc) rc = read_member_flags(ctx, batch, true, flags_host, flags_dev);
+  }
+  if (rc) return rc;
+  if (!small) {
+    // a_b = first row of the solved right-hand-side block; log det and a^T a per member
+    G3_HIP(hipMemcpy2DAsync(a, (size_t)Np * es, rhs, (size_t)kstride * es, (size_t)Np * es, (size_t)batch,
+                            hipMemcpyDeviceToDevice, ctx->stream));
+    rc = g3i_logp_terms_dev(ctx, K, N, ldk, a, dt, dstats, batch, kstride, Np);
+  }
+  return rc;
 }
 
 static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch, const void* X, int64_t N,
@@ -961,33 +999,8 @@ static int gp_factor_batched_impl(g3_ctx* ctx, const MemberProgs& mp, int batch,
   if (!rc && !small) rc = pad_row_launch(ctx, rhs, ldk, delta, N, Np, RB, dt, batch, kstride, ldd);
   g3i_prof_end(ctx, pr);
   if (rc) return rc;
-  pr = g3i_prof_begin(ctx, G3_TAG_POTRF, (double)batch * ((double)N * N * N / 3.0 + (double)N * N));
-  if (small) {
-    rc = g3i_small_factor_batched(ctx, K, ldk, kstride, invd, wstride, delta, ldd, a, Np, dstats, batch, N, Np, dt);
-    g3i_prof_end(ctx, pr);
-    if (!rc) rc = read_member_flags(ctx, batch, false);
-  } else if (Np <= ctx->tune.coop_max_n && batch >= ctx->tune.coop_min_batch) {
-    // long chains of medium members: a group of workgroups per member, the whole batch in ONE launch (g3_chainb.hip): 1.2 -
-    // 1.3x the lock-step sweep below at N <= 512, 1.08x at 768 - 1024; short batches (< ~200 members) stay with the sweep,
-    // whose launches are at least as wide as the batch (profiles/r05_chain_medium.txt)
-    rc = g3i_coop_factor_batched(ctx, K, ldk, kstride, invd, wstride, (unsigned*)dm.tail, batch, Np, dt);
-    g3i_prof_end(ctx, pr);
-    if (!rc) rc = read_member_flags(ctx, batch, false);
-  } else {
-    // one sweep factors every member; a member whose pivot fails only stops its own launches
-    g3_batch_scope mode(ctx, batch, kstride, wstride, invd, (size_t)batch * wstride * es);
-    rc = g3i_potrf_tall(ctx, K, Np, ldk, dt, invd, RB);
-    g3i_prof_end(ctx, pr);
-    if (!rc) rc = read_member_flags(ctx, batch, true);
-  }
+  rc = g3i_factor_members(ctx, batch, N, Np, delta, ldd, dt, K, ldk, kstride, invd, a, dstats, (unsigned*)dm.tail, ctx->h_info, nullptr);
   if (rc) return rc;
-  if (!small) {
-    // a_b = first row of the solved right-hand-side block; log det and a^T a per member
-    G3_HIP(hipMemcpy2DAsync(a, (size_t)Np * es, rhs, (size_t)kstride * es, (size_t)Np * es, (size_t)batch,
-                            hipMemcpyDeviceToDevice, ctx->stream));
-    rc = g3i_logp_terms_dev(ctx, K, N, ldk, a, dt, dstats, batch, kstride, Np);
-    if (rc) return rc;
-  }
   double* hst = (double*)malloc(sbytes);
   if (!hst) return G3_ERR_NOMEM;
   if (hipMemcpyAsync(hst, dstats, sbytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

@@ -1,5 +1,5 @@
 // The fused gradient entry points on a finished factor, for one member or a chain's members in the grid: K^-1 and alpha from what
-// g3_gp_factor(_batched) left (kinv_alpha), then g3_gram_grad's kernel-parameter sums (g3_grad.hip) with K^-1 as the weight
+// g3_gp_factor(_batched) left (g3i_kinv_alpha), then g3_gram_grad's kernel-parameter sums (g3_grad.hip) with K^-1 as the weight
 // (g3_gp_dlogp*: log marginal likelihood) or with the weight below (g3_gp_dloo*: leave-one-out score, no counterpart in the reference).
 //
 // The leave-one-out weight.  With A = K^-1 of the factored covariance, alpha = A delta and c = diag A, the part of g3_gp_loo's
@@ -44,8 +44,8 @@ int g3i_kinv_sweep(g3_ctx* ctx, int batch, const void* L, int64_t np, int64_t ld
 
 // `batch` members after one factorisation sweep (L, Y, Kinv kstride elements apart, block inverses Np * 128, vectors Np; one member:
 // kstride 0): Y = L^-T and Kinv = Y Y^T in ONE sweep recorded under `tag`, alpha_b = Y_b a_b (rows of Y dotted with a) in one launch
-static int kinv_alpha(g3_ctx* ctx, int batch, const void* L, int64_t N, int64_t ldl, int64_t kstride, const void* invd, const void* a,
-                      g3_dtype dt, void* Y, int64_t ldy, void* Kinv, int64_t ldc, void* alpha, int tag) {
+int g3i_kinv_alpha(g3_ctx* ctx, int batch, const void* L, int64_t N, int64_t ldl, int64_t kstride, const void* invd, const void* a,
+                   g3_dtype dt, void* Y, int64_t ldy, void* Kinv, int64_t ldc, void* alpha, int tag) {
   const int64_t Np = g3_roundup(N, G3_LB);
   const int rc = g3i_kinv_sweep(ctx, batch, L, Np, ldl, kstride, invd, dt, Y, ldy, Kinv, ldc, tag, 2.0 * (double)batch * (double)N * N * N / 3.0);
   if (rc) return rc;
@@ -70,7 +70,7 @@ static int fields_call_expanded(const g3_kernel_prog* tmpl, int batch, const dou
 static int dlogp_core(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const g3_grad_map* map, const void* X, int64_t N,
                       int64_t ldx, int d, const void* L, int64_t ldl, int64_t kstride, const void* invd, const void* a, g3_dtype dt,
                       void* Y, int64_t ldy, void* Kinv, int64_t ldc, void* alpha, double* out_host) {
-  const int rc = kinv_alpha(ctx, batch, L, N, ldl, kstride, invd, a, dt, Y, ldy, Kinv, ldc, alpha, G3_TAG_POTRF);
+  const int rc = g3i_kinv_alpha(ctx, batch, L, N, ldl, kstride, invd, a, dt, Y, ldy, Kinv, ldc, alpha, G3_TAG_POTRF);
   if (rc) return rc;
   return g3i_gram_grad_batched(ctx, progs, batch, map, X, N, ldx, d, dt, Kinv, ldc, kstride, alpha, g3_roundup(N, G3_LB), out_host);
 }
@@ -221,7 +221,7 @@ static int dloo_core(g3_ctx* ctx, const g3_kernel_prog* progs, int batch, const 
   if (rc) return rc;
   char* t = zero + zbytes;
   char* M = t + tbytes;
-  rc = kinv_alpha(ctx, batch, L, N, ldl, kstride, invd, a, dt, Y, ldy, Kinv, ldc, alpha, G3_TAG_TRSM);
+  rc = g3i_kinv_alpha(ctx, batch, L, N, ldl, kstride, invd, a, dt, Y, ldy, Kinv, ldc, alpha, G3_TAG_TRSM);
   if (rc) return rc;
   G3_HIP(hipMemsetAsync(zero, 0, (size_t)Np * es, ctx->stream));
   const unsigned nt = (unsigned)(Np / DL_T);

@@ -754,5 +754,51 @@ static inline int g3h_args_padded_out(const void* P, int64_t ld, int64_t N, size
   if (ld < g3h_roundup(N, G3H_LB) || ld % (16 / (int64_t)es)) return -(at + 1);
   return 0;
 }
+// the folds of g3_gp_cv: idx, ptr, nfold at `at`, at + 1, at + 2.  Fold f is idx[ptr[f] .. ptr[f + 1]); nfold in 1 .. G3_MAX_BATCH
+// (looked at first: it says how many pointers there are), ptr[0] = 0 and no pointer below the one before it, every index in
+// [0, N) and in at most one place over all folds (the first offence in idx's order decides).  A fold may be empty, the folds
+// need not cover [0, N), and idx may be null when they hold nothing.  G3_ERR_NOMEM: no memory for the N marks.
+static inline int g3h_args_folds(const int32_t* idx, const int64_t* ptr, int nfold, int64_t N, int at) {
+  if (nfold < 1 || nfold > G3_MAX_BATCH) return -(at + 2);
+  if (!ptr || ptr[0] != 0) return -(at + 1);
+  for (int f = 0; f < nfold; ++f)
+    if (ptr[f + 1] < ptr[f]) return -(at + 1);
+  const int64_t total = ptr[nfold];
+  if (total == 0) return 0;
+  if (!idx) return -at;
+  unsigned char* seen = (unsigned char*)calloc((size_t)N, 1);
+  if (!seen) return G3_ERR_NOMEM;
+  int rc = 0;
+  for (int64_t k = 0; k < total && !rc; ++k) {
+    const int64_t i = idx[k];
+    if (i < 0 || i >= N || seen[i]) rc = -at;
+    else seen[i] = 1;
+  }
+  free(seen);
+  return rc;
+}
+// Launch groups of g3_gp_cv: consecutive folds whose members -- `per(Sp)` bytes each at Sp = roundup(largest fold of the group,
+// 128), at least 128 -- fit in `cap` bytes together; a fold too large for that alone is its own group.  first[g] .. first[g + 1]
+// are group g's folds, sp[g] its Sp.
+template <typename Per>
+static inline void g3h_fold_groups(const int64_t* ptr, int nfold, size_t cap, Per&& per, std::vector<int>* first, std::vector<int64_t>* sp) {
+  first->assign(1, 0);
+  sp->clear();
+  int64_t cur = G3H_LB;
+  for (int f = 0; f < nfold; ++f) {
+    const int64_t s = ptr[f + 1] - ptr[f];
+    const int64_t want = g3h_roundup(s > cur ? s : cur, G3H_LB);
+    const int have = f - first->back();
+    if (have > 0 && (size_t)(have + 1) * per(want) > cap) {
+      sp->push_back(cur);
+      first->push_back(f);
+      cur = g3h_roundup(s > G3H_LB ? s : G3H_LB, G3H_LB);
+    } else {
+      cur = want;
+    }
+  }
+  sp->push_back(cur);
+  first->push_back(nfold);
+}
 // a *_batched_fields entry point's status from its whole-programs body's: lo .. -4 name arguments three places further there
 static inline int g3h_fields_status(int rc, int lo) { return (rc <= -4 && rc >= lo) ? rc - 3 : rc; }

@@ -320,6 +320,18 @@ int g3i_potri(g3_ctx* ctx, const void* L, int64_t n, int64_t ldl, const void* in
 // member's pivot flag cleared, recorded as one profiler region `tag` of `flops`
 int g3i_kinv_sweep(g3_ctx* ctx, int batch, const void* L, int64_t np, int64_t ldl, int64_t kstride, const void* invd, g3_dtype dt,
                    void* Y, int64_t ldy, void* Kinv, int64_t ldc, int tag, double flops);
+// that sweep with Kinv = Y Y^T, then alpha_b = Y_b a_b in one launch (vectors roundup(N,128) apart; one member: kstride 0)
+int g3i_kinv_alpha(g3_ctx* ctx, int batch, const void* L, int64_t N, int64_t ldl, int64_t kstride, const void* invd, const void* a,
+                   g3_dtype dt, void* Y, int64_t ldy, void* Kinv, int64_t ldc, void* alpha, int tag);
+// What g3_gp_factor_batched queues behind its Gram launch, for `batch` prepared members in its layout (K: (Np + 128) x ldk each,
+// kstride apart, identity-padded from N on; block inverses Np * 128 apart, a batch x Np, dstats four doubles per member): factor,
+// a_b = L_b^-1 delta_b, the four scalars of g3_logp_terms.  Np <= 256: g3i_small_factor_batched, which reads the right-hand sides
+// from delta (ldd apart); larger: the right-hand-side block of every member must hold [delta_b; 0], and the members go through the
+// cooperative kernel (coop_ctl: its control words; null: never) or one lock-step sweep -- a batch of one is the single-matrix
+// sweep.  The members' pivot flags are copied to flags_host (valid once the stream is synchronised) and, when flags_dev is
+// given, there as well; the context's flags are left cleared.  No host synchronisation.
+int g3i_factor_members(g3_ctx* ctx, int batch, int64_t N, int64_t Np, const void* delta, int64_t ldd, g3_dtype dt, void* K, int64_t ldk,
+                       int64_t kstride, void* invd, void* a, double* dstats, unsigned* coop_ctl, int* flags_host, int* flags_dev);
 
 // ---- the members of a chain (MemberProgs, g3_host.h) as the batched entry points use them
 // Every member must be a valid program of ONE structure (whole programs), or the template and member 0 valid (template form:

@@ -507,6 +507,22 @@ class Device:
                                         self._ptr(Y), alpha.ptr, kdiag.ptr)
         _check(self, rc, 'g3_gp_loo_batched')
 
+    # ---- leave-fold-out cross-validation from the factor
+    def gp_cv(self, N, L, W, a, Y, Kinv, alpha, idx, ptr, resid, pvar):
+        """after gp_factor: K^-1 and alpha as gp_dlogp leaves them, then for the folds idx[ptr[f]:ptr[f + 1]] (int32 indices,
+        int64 pointers) resid = A_II^-1 alpha_I and pvar = diag A_II^-1 scattered to the observations (roundup(N) entries each,
+        0 in no fold and from N on); returns (fold, info): fold (F, 2) = log det A_II and alpha_I^T A_II^-1 alpha_I, info (F,) the
+        folds' pivot flags.  Synchronises; the caller downloads resid and pvar"""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+        F = len(ptr) - 1
+        fold, info = np.empty((max(F, 1), 2)), np.zeros(max(F, 1), dtype=np.int32)
+        rc = self.lib.g3_gp_cv(self.ctx, L.ptr, N, L.ld, W.ptr, a.ptr, _lib.dtype_code(L.dtype), Y.ptr, Y.ld, Kinv.ptr, Kinv.ld,
+                               alpha.ptr, idx.ctypes.data, ptr.ctypes.data, F, resid.ptr, pvar.ptr, fold.ctypes.data,
+                               info.ctypes.data)
+        _check(self, rc, 'g3_gp_cv')
+        return fold[:F], info[:F]
+
     # ---- gradient of the leave-one-out log predictive
     def gp_dloo(self, prog, gmap, X, N, d, L, W, a, Y, Kinv, alpha, kdiag, u):
         """after gp_factor: K^-1, alpha = K^-1 delta, kdiag = diag K^-1, u = K^-1 (alpha / kdiag) (roundup(N) entries each,

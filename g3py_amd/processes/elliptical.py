@@ -203,7 +203,7 @@ class EllipticalProcess(StochasticProcess):
                 sp = None
             st, cross = self._dist_step(c, values, dl, sp)
             st['delta_finite'] = bool(finite)
-            c['stats'], c['which'], c['grad'], c['cross'], c['loo'] = st, which, None, cross, None
+            c['stats'], c['which'], c['grad'], c['cross'], c['loo'], c['cv'] = st, which, None, cross, None, None
             return st
         dvec = self._workspace['dvec']
         dev.copy_in(dvec, np.where(np.isfinite(dl), dl, 0).astype(self.dtype))
@@ -214,6 +214,7 @@ class EllipticalProcess(StochasticProcess):
         c['grad'] = None            # K^-1 / alpha pieces of th_dlogp belong to this factorisation
         c['cross'] = None           # so does the last cross solve
         c['loo'] = None             # and the leave-one-out vectors
+        c['cv'] = None              # and the leave-fold-out ones
         return st
 
     def _cross(self, c, values, space, noise, kernel=None):

@@ -88,6 +88,92 @@ def loo_assemble(alpha, kdiag, z, mapping, values, y=None, dtype=np.float64, her
     return out
 
 
+def parse_folds(folds, N):
+    """The folds of `cv` as a list of int64 index arrays into the N observations, from
+        an int k                    np.array_split(np.arange(N), k): contiguous blocks
+        a length-N integer array    labels; observations that share a label >= 0 form a fold (in the order of the labels),
+                                    a negative label is in no fold
+        a sequence of index arrays  as given
+    Anything else, and the first offence of a sequence -- an index outside [0, N), an index in two places, more than 4096
+    folds -- is a ValueError.  No device: a pure function."""
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, (bool, np.bool_)):
+        if folds < 1:
+            raise ValueError('cv needs at least one fold, got %d' % folds)
+        if folds > _lib.G3_MAX_BATCH:
+            raise ValueError('more than %d folds (%d)' % (_lib.G3_MAX_BATCH, folds))
+        return [a.astype(np.int64) for a in np.array_split(np.arange(N), int(folds))]
+    if isinstance(folds, (str, bytes, dict)) or not hasattr(folds, '__len__'):
+        raise ValueError('folds: an int, a length-N array of integer labels or a sequence of index arrays, not %r' % type(folds).__name__)
+    flat = None
+    try:
+        flat = np.asarray(folds)
+    except ValueError:          # ragged: a sequence of index arrays
+        pass
+    if flat is not None and flat.ndim == 1 and flat.dtype != object and len(flat) > 0:
+        if not np.issubdtype(flat.dtype, np.integer):
+            raise ValueError('fold labels must be integers, not %s' % flat.dtype)
+        if len(flat) != N:
+            raise ValueError('%d fold labels for %d observations' % (len(flat), N))
+        labels = np.unique(flat[flat >= 0])
+        if len(labels) > _lib.G3_MAX_BATCH:
+            raise ValueError('more than %d folds (%d)' % (_lib.G3_MAX_BATCH, len(labels)))
+        return [np.flatnonzero(flat == u).astype(np.int64) for u in labels]
+    if len(folds) == 0:
+        raise ValueError('cv needs at least one fold')
+    if len(folds) > _lib.G3_MAX_BATCH:
+        raise ValueError('more than %d folds (%d)' % (_lib.G3_MAX_BATCH, len(folds)))
+    out, seen = [], np.zeros(N, dtype=bool)
+    for f, one in enumerate(folds):
+        a = np.asarray(one)
+        if a.ndim != 1 or (len(a) and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError('fold %d is not a one-dimensional array of integer indices' % f)
+        a = a.astype(np.int64)
+        for i in a:
+            if i < 0 or i >= N:
+                raise ValueError('fold %d: index %d is out of range for %d observations' % (f, i, N))
+            if seen[i]:
+                raise ValueError('fold %d: index %d is in two folds (overlap)' % (f, i))
+            seen[i] = True
+        out.append(a)
+    return out
+
+
+def cv_assemble(resid, pvar, fold, info, folds, z, mapping, values, y, dtype=np.float64, hermite=None, mean=True, std=True,
+                var=False, median=False, logpred=True):
+    """The O(N) host side of leave-fold-out cross-validation, from what g3_gp_cv returns: resid_i = [A_II^-1 alpha_I]_i and
+    pvar_i = [A_II^-1]_ii for the fold I that holds i, so that observation i given everything outside its fold is latent-normal
+    with loc_i = z_i - resid_i and variance pvar_i -- loo_assemble's formulas at alpha' = resid / pvar, kdiag' = 1 / pvar -- and
+    per fold (log det A_II, alpha_I^T A_II^-1 alpha_I).  Returns a DictObj under loo's keys: the curves have length N with NaN at
+    observations in no fold; `logpredictive` sums the held-out points' marginal log densities; `logpredictive_joint` sums over
+    the folds log p(y_I | rest) = -1/2 quad + 1/2 logdet - |I| / 2 log 2 pi plus the warp's logdet_dinv of the held-out y.  A fold
+    with a non-zero pivot flag sends both scores to the -1e30 sentinel.  `folds` and `info` are handed through.  No device, no
+    process: a pure function of its arguments."""
+    t = np.dtype(dtype).type
+    N = len(z)
+    held = np.concatenate([np.asarray(f, dtype=np.int64) for f in folds]) if len(folds) else np.zeros(0, dtype=np.int64)
+    resid, pvar, z, y = (np.asarray(v, dtype=dtype) for v in (resid, pvar, z, y))
+    with np.errstate(all='ignore'):
+        part = loo_assemble(resid[held] / pvar[held], t(1) / pvar[held], z[held], mapping, values, y=y[held], dtype=dtype,
+                            hermite=hermite, mean=mean, std=std, var=var, median=median, logpred=logpred)
+    from ..libs import DictObj
+    out = DictObj()
+    for k in ('mean', 'variance', 'std', 'median'):
+        if k in part:
+            out[k] = np.full(N, np.nan, dtype=dtype)
+            out[k][held] = part[k]
+    if logpred:
+        bad = bool(np.any(np.asarray(info) != 0))
+        out['logpredictive'] = t(SENTINEL) if bad else part['logpredictive']
+        fold = np.asarray(fold, dtype=np.float64).reshape(-1, 2)
+        with np.errstate(all='ignore'):
+            det_m = mapping.logdet_dinv(y[held], values) if len(held) else 0.0
+            joint = (-0.5 * fold[:, 1] + 0.5 * fold[:, 0]).sum() - 0.5 * len(held) * np.log(2.0 * np.pi) + det_m
+        out['logpredictive_joint'] = t(SENTINEL) if bad or not np.isfinite(joint) else t(joint)
+    out['folds'] = list(folds)
+    out['info'] = np.asarray(info)
+    return out
+
+
 class _Ref:
     """placeholder a kernel's spec() carries where a free hyper-parameter's value would go"""
 
@@ -662,11 +748,11 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
     #      harness, models.py:449-469, refits per hold-out split)
     _LOO_HERMITE = None          # mean / variance of a plain process: mapping(loc) and sd^2 (elliptical.py:190-200)
 
-    def _loo_guard(self, inputs=None):
+    def _loo_guard(self, inputs=None, what='loo'):
         if self._dist is not None:
-            raise _lib.G3Error('loo runs on one GPU')
+            raise _lib.G3Error(what + ' runs on one GPU')
         if inputs is None and not self.is_observed:
-            raise _lib.G3Error('loo needs observations')
+            raise _lib.G3Error(what + ' needs observations')
 
     def loo(self, params=None, inputs=None, outputs=None, mean=True, std=True, var=False, median=False, logpred=True):
         """Every observation predicted from all the others, from the Cholesky factor `logp` already paid for: a DictObj
@@ -694,6 +780,44 @@ class GaussianProcess(FactorLikelihood, EllipticalProcess):
                            hermite=self._LOO_HERMITE, mean=mean, std=std, var=var, median=median, logpred=logpred)
         if logpred and (const or not np.isfinite(st['logdet']) or st['nonfinite'] > 0):           # gaussian.py:234-237
             out['logpredictive'] = self.dtype.type(SENTINEL)
+        return out
+
+    def cv(self, params=None, folds=5, inputs=None, outputs=None, mean=True, std=True, var=False, median=False, logpred=True):
+        """Blocked / k-fold cross-validation from the Cholesky factor `logp` already paid for: every fold predicted from all
+        the observations outside it, without a refit.  `folds`: an int k (k contiguous blocks, the blocked-CV default), a
+        length-N array of integer labels (negative: in no fold) or a sequence of index arrays (parse_folds).  Returns a DictObj
+        under loo's keys -- mean, variance, std, median of length N: each observation's marginal predictive given everything
+        outside its fold, NaN in no fold; `logpredictive`, the sum of the held-out points' marginal log densities (what loo and
+        th_logpredictive report) -- plus `logpredictive_joint`, the sum over folds of log p(y_I | rest), `folds`, the index
+        arrays used, and `info`, the folds' pivot flags.  With A = K^-1 of the factored covariance and alpha = A delta the fold's
+        latent predictive is N(z_I - A_II^-1 alpha_I, A_II^-1): the device forms K^-1 and factors every A_II in batched
+        launches (g3_gp_cv: 2 N^3 / 3 + 2 sum_f s_f^3 / 3 flops), the host the O(N) rest (cv_assemble).  F = N folds of one point
+        is loo; one fold of everything is the prior, its joint score loglike.  A `logp` on the same parameters before it is
+        not repeated, and the result is kept per (factorisation, folds).  Where th_loglike takes its constant branch, and
+        where a fold's factorisation reports a pivot, both scores are the -1e30 sentinel."""
+        self._loo_guard(inputs, 'cv')
+        params, _, inputs, outputs, _ = self._call_defaults(params, None, inputs, outputs, False, False)
+        dev = self.device
+        values, _ = self._values(params)
+        c = self._factor(values, inputs, outputs)
+        N, Np = c['N'], c['Np']
+        fl = parse_folds(folds, N)
+        idx = np.concatenate(fl).astype(np.int32) if fl else np.zeros(0, dtype=np.int32)
+        ptr = np.concatenate([[0], np.cumsum([len(f) for f in fl])]).astype(np.int64)
+        key = (idx.tobytes(), ptr.tobytes())
+        const = not (np.all(np.isfinite(c['delta'])) and np.all(np.isfinite(c['det_m'])))     # gaussian.py:234-235
+        st = self._solve(c, values, 'post' if const else 'logp')
+        got = c.get('cv')
+        if got is None or got['stats'] is not st or got['key'] != key:       # (kept with the factorisation it belongs to)
+            Y, Kinv, alpha, vec = self._kinv_workspace(Np, vec='cv')        # (Y, Kinv and alpha: dlogp's, scratch in both)
+            fold, info = dev.gp_cv(N, c['Kd'], c['Wd'], c['ad'], Y, Kinv, alpha, idx, ptr, vec,
+                                   dev.wrap(vec.offset(1), 1, Np, Np, self.dtype, keep=vec))
+            rv = dev.download(vec, 2, N)
+            got = c['cv'] = dict(stats=st, key=key, resid=rv[0], pvar=rv[1], fold=fold, info=info)
+        out = cv_assemble(got['resid'], got['pvar'], got['fold'], got['info'], fl, c['z'], self.f_mapping, values, c['y'],
+                          dtype=self.dtype, hermite=self._LOO_HERMITE, mean=mean, std=std, var=var, median=median, logpred=logpred)
+        if logpred and (const or not np.isfinite(st['logdet']) or st['nonfinite'] > 0):           # gaussian.py:234-237
+            out['logpredictive'] = out['logpredictive_joint'] = self.dtype.type(SENTINEL)
         return out
 
     def loo_chain(self, chain, batch=None):

@@ -451,7 +451,10 @@ class StochasticProcess:
         (boundary: models.py:449-469 -- the keys `_l1`, `_l2`, `_mse`, `_rmse`, `_median_l1`,
         `_median_l2`, `_logp`, `_loglike`, `_logprior`, `_nlpd`).  loo=True (keyword only; no counterpart in the reference) adds the
         leave-one-out scores of the OBSERVATIONS from the factor logp already paid for (GaussianProcess.loo): `_loo_nlpd`
-        = -logpredictive / N, `_loo_l1` and `_loo_l2`, the mean absolute and squared error of the leave-one-out mean"""
+        = -logpredictive / N, `_loo_l1` and `_loo_l2`, the mean absolute and squared error of the leave-one-out mean.  cv=folds
+        (keyword only, taken from **kwargs so that the signature stays what callers introspect; what GaussianProcess.cv takes as
+        `folds`) adds the same three for blocked / k-fold cross-validation
+        over the observations held out by some fold: `_cv_nlpd` = -logpredictive / n_held, `_cv_l1` and `_cv_l2`"""
         truth = self.hidden if hidden is None else hidden
         pred = self.predict(params=params, space=space, inputs=inputs, outputs=outputs, mean=True, var=variance,
                             median=median, distribution=logpred)
@@ -478,6 +481,16 @@ class StochasticProcess:
             seen = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
             out.update(_loo_nlpd=-held.logpredictive / len(seen), _loo_l1=np.mean(np.abs(held.mean - seen)),
                        _loo_l2=np.mean((held.mean - seen) ** 2))
+        cv = kwargs.pop('cv', None)
+        if cv is not None:
+            if not hasattr(self, 'cv'):
+                from .._lib import G3Error
+                raise G3Error('cross-validation scores are not available for %s' % type(self).__name__)
+            held = self.cv(params=params, folds=cv, inputs=inputs, outputs=outputs, mean=True, std=False, logpred=True)
+            seen = np.asarray(self.outputs if outputs is None else outputs, dtype=self.dtype).reshape(-1)
+            out_of = np.concatenate(held.folds)
+            miss = held.mean[out_of] - seen[out_of]
+            out.update(_cv_nlpd=-held.logpredictive / len(out_of), _cv_l1=np.mean(np.abs(miss)), _cv_l2=np.mean(miss ** 2))
         return out
 
     def logp_chain(self, chain, prior=False):

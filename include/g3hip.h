@@ -437,6 +437,34 @@ int g3_gp_loo(g3_ctx* ctx, const void* L_dev, int64_t N, int64_t ldl, const void
 int g3_gp_loo_batched(g3_ctx* ctx, int batch, const void* L_dev, int64_t N, int64_t ldl, int64_t kstride, const void* invd_dev,
                       const void* a_dev, g3_dtype dt, void* Y_dev, void* alpha_dev, void* kdiag_dev);
 
+/* ---- leave-fold-out cross-validation from the factor (no counterpart in the reference: models.py:449-469 and
+ * selection.py:237-292 observe the complement, refactor and predict once per fold) ------------------------------------------
+ * After g3_gp_factor on the same buffers, with arguments 2 .. 12 and their checks as g3_gp_dlogp's factor, Y, Kinv and alpha
+ * (N between L_dev and ldl, dt looked at first, as g3_gp_loo).  With A = K^-1 of the factored covariance and alpha = A delta,
+ * a fold with index set I, conditioned on every observation outside it, is
+ *     z_I | rest ~ N(z_I - r_I, A_II^-1),   r_I = A_II^-1 alpha_I,
+ *     log p(z_I | rest) = -1/2 alpha_I^T A_II^-1 alpha_I + 1/2 log det A_II - |I| / 2 log 2 pi.
+ * Fold f is idx_host[ptr_host[f] .. ptr_host[f + 1]): ptr_host[0] = 0, no pointer below the one before it (-14), every index
+ * in [0, N) and in at most one place over all folds (-13), 1 <= nfold <= 4096 (-15).  A fold may be empty and the folds need
+ * not cover the observations.  A refused call launches nothing and writes nothing.
+ * Steps: g3_potri (Y_dev <- L^-T, lower triangle of Kinv_dev <- K^-1, 2 N^3 / 3 flops) and alpha_dev = Y a, as g3_gp_dlogp;
+ * one gather launch per group of folds that writes every fold as a member in g3_gp_factor_batched's layout, (Sp + 128) x Sp
+ * with Sp = roundup(largest fold of the group, 128), into the context's workspace -- the lower triangle of A[I, I] (nothing
+ * above Kinv's diagonal is read), the identity from the fold's size on, the right-hand-side block [alpha_I; 0]; the
+ * factorisation launches of g3_gp_factor_batched on those members (Sp <= 256: one workgroup per member; larger: one lock-step
+ * sweep, never the cooperative kernel; no jitter schedule); g3_gp_loo_batched on them (Sp > 256: one member at a time, Y_dev
+ * its workspace); one scatter launch per group.  sum_f s_f^3 / 3 flops for the factors and as much for their inverses; a
+ * group holds at most 256 MB of members, a fold too large for that alone is its own group.
+ * resid_dev[i] = [r_I]_i and pvar_dev[i] = [A_II^-1]_ii for i in fold I, the marginal variance of z_i given everything
+ * outside its fold: roundup(N,128) entries each, 0 for observations in no fold and from N on.  fold_host[2 f] = log det
+ * A_II, fold_host[2 f + 1] = alpha_I^T A_II^-1 alpha_I, info_host[f] = the fold's pivot flag; a fold with a non-zero flag has
+ * NaN in both scalars and in its entries of resid_dev and pvar_dev.  On return Kinv_dev and alpha_dev are as g3_gp_dlogp
+ * leaves them and Y_dev is unspecified.  No atomics, every sum in a fixed order: two calls give the same bits.  Synchronises
+ * once, like g3_gp_dlogp; G3_ERR_NOMEM when the workspace cannot be had. */
+int g3_gp_cv(g3_ctx* ctx, const void* L_dev, int64_t N, int64_t ldl, const void* invd_dev, const void* a_dev, g3_dtype dt,
+             void* Y_dev, int64_t ldy, void* Kinv_dev, int64_t ldc, void* alpha_dev, const int32_t* idx_host,
+             const int64_t* ptr_host, int nfold, void* resid_dev, void* pvar_dev, double* fold_host, int* info_host);
+
 /* ---- reverse mode through the Cholesky factor ------------------------------------------------------------------------------
  * CholeskyRobust.grad (g3py/libs/tensors.py:224-260, Murray 2016): given the factor L (lower) and Lbar = d f / d L,
  *     Kbar = tril(S + S^T) - diag(S),   S = L^-T Phi(tt_to_num(L^T Lbar)) L^-1,   Phi = tril with halved diagonal
