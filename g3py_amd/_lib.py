@@ -141,6 +141,9 @@ _SIGS = {
     'g3_gp_loo': ([_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _I64, _P, _P], C.c_int),
     'g3_gp_loo_batched': ([_P, C.c_int, _P, _I64, _I64, _I64, _P, _P, C.c_int, _P, _P, _P], C.c_int),
     'g3_gp_cv': ([_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _I64, _P, _I64, _P, _P, _P, C.c_int, _P, _P, _P, _P], C.c_int),
+    'g3_gp_cross_dx': ([_P, C.POINTER(KernelProg), _P, _I64, _I64, _P, _I64, _I64, C.c_int, C.c_int, _P, _P, _I64, _P, _I64,
+                        _P, _I64, _P, _P, _I64], C.c_int),
+    'g3_gram_diag_dx': ([_P, C.POINTER(KernelProg), _P, _I64, _I64, C.c_int, C.c_int, _P, _I64], C.c_int),
     'g3_potrf_vjp': ([_P, _P, _I64, _P, _I64, _I64, C.c_int, _P, _I64], C.c_int),
     'g3_gram_vjp': ([_P, C.POINTER(KernelProg), C.POINTER(GradMap), _P, _I64, _I64, C.c_int, C.c_int, _P, _I64,
                      C.POINTER(C.c_double)], C.c_int),

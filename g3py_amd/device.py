@@ -507,6 +507,24 @@ class Device:
                                         self._ptr(Y), alpha.ptr, kdiag.ptr)
         _check(self, rc, 'g3_gp_loo_batched')
 
+    # ---- gradients of the posterior pieces with respect to the query inputs
+    def gp_cross_dx(self, prog, Xs, M, X, N, d, alpha, V, Y, W, dmu, dss):
+        """after gp_loo (Y = L^-T, alpha = K^-1 delta) and gp_cross (V) for the same Xs and program:
+        dmu[i, c] = sum_j alpha_j d1_c k(xs_i, x_j) and dss[i, c] = 2 sum_j W_ij d1_c k(xs_i, x_j), W = V Y^T (roundup(M) x
+        roundup(N) workspace), into M x d device matrices; either output may be None, and alpha is needed for dmu only, V, Y
+        and W for dss only.  Stream-ordered, the caller downloads"""
+        out = dmu if dmu is not None else dss
+        rc = self.lib.g3_gp_cross_dx(self.ctx, C.byref(prog), Xs.ptr, M, Xs.ld, X.ptr, N, X.ld, d, _lib.dtype_code(X.dtype),
+                                     self._ptr(alpha), self._ptr(V), V.ld if V is not None else 0, self._ptr(Y),
+                                     Y.ld if Y is not None else 0, self._ptr(W), W.ld if W is not None else 0, self._ptr(dmu),
+                                     self._ptr(dss), out.ld if out is not None else 0)
+        _check(self, rc, 'g3_gp_cross_dx')
+
+    def gram_diag_dx(self, prog, Xs, M, d, dk):
+        """dk[i, c] = d k(x, x) / d x_c at x = xs_i (M x d device matrix): the derivative of gram_diag's output"""
+        rc = self.lib.g3_gram_diag_dx(self.ctx, C.byref(prog), Xs.ptr, M, Xs.ld, d, _lib.dtype_code(dk.dtype), dk.ptr, dk.ld)
+        _check(self, rc, 'g3_gram_diag_dx')
+
     # ---- leave-fold-out cross-validation from the factor
     def gp_cv(self, N, L, W, a, Y, Kinv, alpha, idx, ptr, resid, pvar):
         """after gp_factor: K^-1 and alpha as gp_dlogp leaves them, then for the folds idx[ptr[f]:ptr[f + 1]] (int32 indices,

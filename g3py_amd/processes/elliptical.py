@@ -11,6 +11,7 @@ import numpy as np
 
 from .. import _lib
 from ..device import Device, compile_spec
+from ..libs import DictObj
 from ..libs.tensors import to_num
 from .hypers import HyperVar
 from .hypers.kernels import Kernel, KernelSum, KernelNoise
@@ -204,6 +205,7 @@ class EllipticalProcess(StochasticProcess):
             st, cross = self._dist_step(c, values, dl, sp)
             st['delta_finite'] = bool(finite)
             c['stats'], c['which'], c['grad'], c['cross'], c['loo'], c['cv'] = st, which, None, cross, None, None
+            c['dx'] = None
             return st
         dvec = self._workspace['dvec']
         dev.copy_in(dvec, np.where(np.isfinite(dl), dl, 0).astype(self.dtype))
@@ -214,6 +216,7 @@ class EllipticalProcess(StochasticProcess):
         c['grad'] = None            # K^-1 / alpha pieces of th_dlogp belong to this factorisation
         c['cross'] = None           # so does the last cross solve
         c['loo'] = None             # and the leave-one-out vectors
+        c['dx'] = None              # and predict_dx's L^-T and alpha
         c['cv'] = None              # and the leave-fold-out ones
         return st
 
@@ -406,6 +409,77 @@ class EllipticalProcess(StochasticProcess):
             dg = dg - ss
         dg = np.where(dg < 0, self.dtype.type(0), dg)
         return loc, np.sqrt(dg), values
+
+    # ---- gradients with respect to the query inputs (in the reference: tt.grad(..., space) through elliptical.py:81-97)
+    def predict_dx(self, params=None, space=None, inputs=None, outputs=None, location=True, kernel_diag=True, kernel_sd=False,
+                   prior=False, noise=False):
+        """Gradients with respect to `space` of what `location`, `kernel_diag` and `kernel_sd` return for the same arguments:
+        a DictObj of (M, d) arrays under those three keys.  These are latent quantities; with the Identity mapping they are the
+        gradients of predict's mean, variance and std.  With alpha = K^-1 delta and w_i = K^-1 k(X, x_i) of the factored
+        (possibly jittered) covariance,
+            d location / d x_i = d m / d x_i + sum_j alpha_j d1 k(x_i, x_j)
+            d diag / d x_i     = d k(x, x) / d x |x_i - 2 sum_j w_ij d1 k(x_i, x_j)
+        d1 being the gradient with respect to the kernel's first argument (g3_gp_cross_dx, g3_gram_diag_dx).  kernel_diag is
+        clipped at 0, and its gradient is 0 where it clips; kernel_sd's is d diag / (2 sd), 0 where sd == 0; the lift tt_to_cov
+        applies to a non-positive prior diagonal with noise=True counts as a constant.  prior=True needs no factor; an
+        unobserved process falls back to the prior, as every method does.  A `predict` at the same space before it shares
+        the cross solve, and L^-T and alpha are kept with the factor: after the first call on a factor a call costs the
+        2 N^2 M product W = V L^-1 plus one pass over the M x N pairs.  Out of scope: a chain of hyper-parameter vectors,
+        the Student-t scaling of a TProcess, and the mapped statistics (mean, variance, quantiles) through a mapping other
+        than Identity."""
+        if self._dist is not None:
+            raise _lib.G3Error('predict_dx runs on one GPU')
+        params, space, inputs, outputs, prior = self._call_defaults(params, space, inputs, outputs, prior, False)
+        values, _ = self._values(params)
+        dev, t = self.device, self.dtype
+        S = self._x(space)
+        M, d = S.shape
+        want_diag = kernel_diag or kernel_sd
+        kern = self.f_kernel_noise if noise else self.f_kernel
+        prog = self._prog(kern, values, d)
+        Sd = dev.upload(S)
+        dloc = np.asarray(self.f_location.dx(S, values), dtype=t) if location else None
+        ddiag = dg = None
+        if want_diag:
+            dk = dev.alloc(M, d, t)
+            dev.gram_diag_dx(prog, Sd, M, d, dk)
+            ddiag = dev.download(dk)
+            dg = self._prior_diag(values, space, noise)
+        if not prior:
+            c = self._factor(values, inputs, outputs)
+            self._solve(c, values, 'post')
+            V, _, ss, _, Mp = self._cross(c, values, space, noise)
+            N, Np = c['N'], c['Np']
+            ws = self._workspace
+            if c.get('dx') is None:
+                # a buffer of its own: dlogp and dloo overwrite the shared scratch ws['Y']
+                if 'dxY' not in ws:
+                    ws['dxY'], ws['dxvec'] = dev.alloc(Np, Np, t), dev.alloc(2, Np, t)
+                vec = ws['dxvec']
+                dev.gp_loo(N, c['Kd'], c['Wd'], c['ad'], ws['dxY'], vec, dev.wrap(vec.offset(1), 1, Np, Np, t, keep=vec))
+                c['dx'] = (ws['dxY'], vec)
+            Y, alpha = c['dx']
+            dmu = dev.alloc(M, d, t) if location else None
+            dss = dev.alloc(M, d, t) if want_diag else None
+            Wm = dev.alloc(Mp, Np, t) if want_diag else None
+            dev.gp_cross_dx(prog, Sd, M, c['Xd'], N, d, alpha, V if want_diag else None, Y if want_diag else None, Wm, dmu, dss)
+            if location:
+                dloc = dloc + dev.download(dmu)
+            if want_diag:
+                ddiag = ddiag - dev.download(dss)
+                dg = dg - ss
+        out = DictObj()
+        if location:
+            out['location'] = dloc
+        if want_diag:
+            ddiag = np.where((dg < 0)[:, None], t.type(0), ddiag)            # tt_to_bounded(., 0) elliptical.py:94-97
+            if kernel_diag:
+                out['kernel_diag'] = ddiag
+            if kernel_sd:
+                sd = np.sqrt(np.where(dg < 0, t.type(0), dg))
+                with np.errstate(all='ignore'):
+                    out['kernel_sd'] = np.where((sd > 0)[:, None], ddiag / (2 * sd)[:, None], t.type(0))
+        return out
 
     def th_median(self, space, inputs, outputs, vector, params, prior=False, noise=False):
         values, _ = self._values(params)

@@ -38,6 +38,18 @@ class Mean(Hypers):
         x = np.asarray(x)
         return self.jac(x[:, self.dims] if self.dims is not None else x, values or {})
 
+    def eval_dx(self, x, values):
+        """d m(x_i) / d x_ic over the columns the mean uses, (M, columns used): what tt.grad(location, space) gives"""
+        raise NotImplementedError('%s has no derivative with respect to its inputs' % type(self).__name__)
+
+    def dx(self, x, values=None):
+        """d m(x_i) / d x_ic as an (M, d) array over ALL the columns of x: zeros in the columns the mean does not use"""
+        x = np.asarray(x)
+        out = np.zeros(x.shape, dtype=x.dtype)
+        cols = self.dims if self.dims is not None else slice(None)
+        out[:, cols] = self.eval_dx(x[:, cols], values or {})
+        return out
+
 Location = Mean
 
 
@@ -46,6 +58,9 @@ class Zero(Mean):
 
     def eval(self, x, values):
         return np.zeros(x.shape[0], dtype=x.dtype)
+
+    def eval_dx(self, x, values):
+        return np.zeros(x.shape, dtype=x.dtype)
 
 
 class Bias(Mean):
@@ -60,6 +75,9 @@ class Bias(Mean):
 
     def jac(self, x, values):
         return [(self.bias, np.ones((x.shape[0], 1), dtype=x.dtype))]
+
+    def eval_dx(self, x, values):
+        return np.zeros(x.shape, dtype=x.dtype)
 
 
 class Linear(Mean):
@@ -78,3 +96,7 @@ class Linear(Mean):
 
     def jac(self, x, values):
         return [(self.constant, np.ones((x.shape[0], 1), dtype=x.dtype)), (self.coeff, x)]
+
+    def eval_dx(self, x, values):
+        coeff = np.asarray(_param(self.coeff, values, x.dtype.type)).reshape(-1)
+        return np.broadcast_to(np.broadcast_to(coeff, (x.shape[1],)), x.shape)

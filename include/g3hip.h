@@ -465,6 +465,36 @@ int g3_gp_cv(g3_ctx* ctx, const void* L_dev, int64_t N, int64_t ldl, const void*
              void* Y_dev, int64_t ldy, void* Kinv_dev, int64_t ldc, void* alpha_dev, const int32_t* idx_host,
              const int64_t* ptr_host, int nfold, void* resid_dev, void* pvar_dev, double* fold_host, int* info_host);
 
+/* ---- gradients of the posterior location and variance with respect to the query inputs (in the reference one
+ * tt.grad(..., space) through the graph of g3py/processes/elliptical.py:81-97) ------------------------------------------------
+ * After g3_gp_factor, g3_gp_loo (Y_dev = its L^-T, alpha_dev = its K^-1 delta) and g3_gp_cross for the same Xs and program
+ * (V_dev = its V).  With d1_c the partial with respect to column c of the FIRST argument of the kernel expression, NOISE
+ * contributing 0 to the cross block:
+ *     dmu[i][c] = sum_j alpha_j d1_c prog(xs_i, x_j);   dss[i][c] = 2 sum_j W_ij d1_c prog(xs_i, x_j),  W = V Y^T  (rows K^-1 k_i)
+ * so that d loc / d xs = d m / d xs + dmu and d diag / d xs = g3_gram_diag_dx - dss (loc and diag as g3_gp_cross's mu and ss
+ * give them).  A jittered factor is differentiated as it was kept.  Steps: W = V Y^T as ONE MFMA product over the padded
+ * sizes (2 N^2 M flops; V's padding columns are zero and Y's the identity, so it is exact), one pass over the M x N pairs that
+ * reads W once and evaluates every leaf and its partials per pair (the interpreter; leave-one-out products over a product's
+ * factors, so a factor may be 0), the column range split over the grid so that M = 1 still fills the chip, and a small launch
+ * that adds the splits in a fixed order: no atomics, two calls give the same bits, and either output alone has the bits of the
+ * joint call.  ceil(d / 8) such launch pairs.  The sums are fp64 for both dtypes.  A leaf value or a partial that is not
+ * finite is added as 0 -- the derivative of the constants tt_to_num (tensors.py:90-92) puts there, which g3_gp_cross applies to
+ * V -- so a query row holding NaN gets zero rows.  dmu_dev, dss_dev: either may be NULL (both: -18); rows i < M, columns c < d
+ * at leading dimension ldg >= d are written, nothing else.  alpha_dev (roundup(N,128)) is needed iff dmu_dev; V_dev, Y_dev and
+ * the roundup(M,128) x roundup(N,128) workspace W_dev (leading dimensions >= roundup(N,128), 16-byte multiples) iff dss_dev.
+ * Arguments are checked in this order, except d (-9) before the leading dimensions measured against it and "no output"
+ * (-18) before the inputs it decides about; a refused call launches nothing.  The partial sums live in the context's
+ * workspace (G3_ERR_HIP when it cannot be had).  Stream-ordered, no host synchronisation. */
+int g3_gp_cross_dx(g3_ctx* ctx, const g3_kernel_prog* prog_cross, const void* Xs_dev, int64_t M, int64_t ldxs,
+                   const void* X_dev, int64_t N, int64_t ldx, int d, g3_dtype dt, const void* alpha_dev,
+                   const void* V_dev, int64_t ldv, const void* Y_dev, int64_t ldy, void* W_dev, int64_t ldw,
+                   void* dmu_dev, void* dss_dev, int64_t ldg);
+/* dk[i][c] = d prog(x, x) / d x_c at x = xs_i, the derivative of g3_gram_diag's output: the square-case diagonal, where every
+ * leaf is symmetric (the pair partial at x' = x, doubled) and NOISE / WN are constants.  Rows i < M, columns c < d at leading
+ * dimension ldg >= d are written.  One launch, stream-ordered. */
+int g3_gram_diag_dx(g3_ctx* ctx, const g3_kernel_prog* prog, const void* Xs_dev, int64_t M, int64_t ldxs, int d, g3_dtype dt,
+                    void* dk_dev, int64_t ldg);
+
 /* ---- reverse mode through the Cholesky factor ------------------------------------------------------------------------------
  * CholeskyRobust.grad (g3py/libs/tensors.py:224-260, Murray 2016): given the factor L (lower) and Lbar = d f / d L,
  *     Kbar = tril(S + S^T) - diag(S),   S = L^-T Phi(tt_to_num(L^T Lbar)) L^-1,   Phi = tril with halved diagonal
