@@ -21,7 +21,15 @@
  *   - Work is enqueued on the context's HIP stream (g3_ctx_set_stream adopts a caller
  *     stream such as torch's current stream).  Functions with host out-parameters
  *     synchronise the stream before returning; functions with only device outputs are
- *     asynchronous.
+ *     asynchronous.  An asynchronous entry reads its device inputs and writes its device outputs in stream order: what
+ *     the caller has queued on that stream before the call is seen, and what the caller queues there after the call returns
+ *     sees the results (the side stream of a two-stream sweep is forked from and joined back into the stream inside the
+ *     call).  Without a host out-parameter and synchronising all the same, each said again where it is declared:
+ *     g3_ctx_set_stream, g3_ctx_sync, g3_ctx_destroy, g3_free, g3_memcpy_h2d, g3_prof_reset and g3_gp_cross_batched(_fields).
+ *     An asynchronous entry may also wait once for a first use -- the compilation of a generated Gram kernel, the ~7 ms
+ *     placement probe of the side stream per (context, stream), the growth of a context workspace or of the context's block
+ *     inverses -- and a Gram entry that uploads a kernel program waits when the ring of G3_PROG_SLOTS (8) program slots has
+ *     wrapped onto a launch that has not run yet.
  *   - One g3_ctx is single-threaded; distinct contexts may be used concurrently.
  */
 #ifndef G3HIP_H
@@ -116,14 +124,18 @@ typedef struct {
 
 /* ---- context and device memory ------------------------------------------------------ */
 int g3_ctx_create(int device, g3_ctx** out);
-int g3_ctx_destroy(g3_ctx* ctx);
+int g3_ctx_destroy(g3_ctx* ctx);   /* synchronises the stream the context works on first */
+/* Synchronises the stream the context has worked on (everything the context queued there, its side stream joined in, is done
+ * when this returns; the caller may then destroy that stream), then adopts hip_stream.  Nothing is waited for on the new
+ * stream: work the caller has queued there stays in front of the context's next call. */
 int g3_ctx_set_stream(g3_ctx* ctx, void* hip_stream /* hipStream_t, NULL = context's own */);
-int g3_ctx_sync(g3_ctx* ctx);
+int g3_ctx_sync(g3_ctx* ctx);      /* hipStreamSynchronize of the stream the context works on */
 const char* g3_last_error(g3_ctx* ctx);
 int g3_version(void);
 
 int g3_malloc(g3_ctx* ctx, size_t bytes, void** dev);
-int g3_free(g3_ctx* ctx, void* dev);
+int g3_free(g3_ctx* ctx, void* dev);   /* synchronises the stream first: queued work may still use the buffer */
+/* synchronises: the host buffer is borrowed for the call only */
 int g3_memcpy_h2d(g3_ctx* ctx, void* dev, const void* host, size_t bytes);
 int g3_memcpy_d2h(g3_ctx* ctx, void* host, const void* dev, size_t bytes);
 int g3_memcpy_d2d(g3_ctx* ctx, void* dst, const void* src, size_t bytes);
@@ -637,7 +649,7 @@ int g3_gp_sample(g3_ctx* ctx, const void* L_dev, int64_t M, int64_t ldl, const v
  * on = 3 times only every 16th of those small launches (a sample, for launch-bound callers). */
 #define G3_PROF_NTAGS 10
 int g3_prof_enable(g3_ctx* ctx, int on);
-int g3_prof_reset(g3_ctx* ctx);
+int g3_prof_reset(g3_ctx* ctx);   /* synchronises the stream: the event records are reused */
 int g3_prof_collect(g3_ctx* ctx, double* out_host /* 3 * G3_PROF_NTAGS */);
 
 /* ---- multi-GPU: the N x N covariance block-partitioned over the GPUs of one node ------------
