@@ -179,6 +179,14 @@ _SIGS = {
     'g3_prof_collect': ([_P, C.POINTER(C.c_double)], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
+# include/g3hip_online.h: appending observations to a factor
+_SIGS_ONLINE = {
+    'g3_gp_append': ([_P, C.POINTER(KernelProg), _P, _I64, _I64, _I64, C.c_int, _P, C.c_int, _P, _I64, _P, _P,
+                      C.POINTER(C.c_double)], C.c_int),
+    'g3_gp_cross_append': ([_P, C.POINTER(KernelProg), _P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, _P, _I64, _P, _P,
+                            C.c_int, _P, _I64, _P, _P], C.c_int),
+}
+EXPORTS_ONLINE = tuple(_SIGS_ONLINE)
 PROF_TAGS = ('gemm_bulk', 'gram', 'potrf', 'trsv', 'cross_gram', 'trsm', 'reduce', 'gemm_mid',
              'gemm_small', 'diag128')
 
@@ -198,7 +206,7 @@ def load():
         raise G3Error('libg3hip.so not found at %s: build it first (make -C g3py_amd/csrc); '
                       'g3py_amd has no CPU fallback' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in _SIGS.items():
+    for name, (args, res) in list(_SIGS.items()) + list(_SIGS_ONLINE.items()):
         f = getattr(lib, name)      # AttributeError if the symbol is missing
         f.argtypes = args
         f.restype = res
@@ -217,3 +225,12 @@ def dtype_code(dtype):
 
 def roundup(n, m=G3_PAD):
     return (int(n) + m - 1) // m * m
+
+
+def append_capacity(have, need):
+    """rows (= leading dimension, a multiple of 128) of a buffer that must hold `need` rows and holds `have`: unchanged while it
+    fits, else at least 1.5 x what it was, so that a run of one-row appends reallocates O(log) times (g3h_append_capacity)"""
+    have, need = int(have), int(need)
+    if need <= have:
+        return have
+    return max(roundup(have + (have + 1) // 2), roundup(need))

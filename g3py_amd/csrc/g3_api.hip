@@ -5,7 +5,7 @@
 #include <stdlib.h>
 
 // ----------------------------------------------------------------------------- context
-extern "C" int g3_version(void) { return 105; }
+extern "C" int g3_version(void) { return 106; }
 
 static int ctx_create_impl(int device, hipStream_t on_stream, g3_ctx** out);
 extern "C" int g3_ctx_create(int device, g3_ctx** out) { return ctx_create_impl(device, nullptr, out); }
@@ -445,18 +445,19 @@ logp_terms_kernel(const T* L, int64_t n, int64_t ld, const T* a, double* out, in
 }
 
 // The tail of one evaluation in ONE launch (small problems are bound by the number of launches, ~5 us each):
-// a_dst <- a_src (the solved right-hand-side row, npad entries), the four scalars of logp_terms_kernel over its
-// first n entries, and the pivot flag handed over and cleared: out[4] = *info, *info = 0.
+// a_dst <- a_src (the solved right-hand-side row, npad entries; from entry a_from on: an append leaves the entries of the
+// rows it did not touch unwritten), the four scalars of logp_terms_kernel over its first n entries, and the pivot flag handed
+// over and cleared: out[4] = *info, *info = 0.
 template <typename T>
 __global__ void __launch_bounds__(1024)
 logp_finish_kernel(const T* L, int64_t n, int64_t npad, int64_t ld, const T* __restrict__ a_src, T* __restrict__ a_dst,
-                   double* out, int* info) {
+                   int64_t a_from, double* out, int* info) {
   __shared__ double red[4][16];
   const int tid = threadIdx.x;
   LogpTerms t;
   for (int64_t i = tid; i < npad; i += 1024) {
     const T av = a_src[i];
-    a_dst[i] = av;
+    if (i >= a_from) a_dst[i] = av;
     if (i < n) {
       t.diag((double)L[i * ld + i]);
       t.rhs((double)av);
@@ -712,6 +713,27 @@ __global__ void pad_row_kernel(T* dst, int64_t ld, const T* src, int64_t n, int6
   for (int64_t r = 0; r < rows; ++r) dst[r * ld + j] = (r == 0 && j < n) ? src[j] : T(0);
 }
 // the right-hand-side block [src; 0] per member: blocks `dstride`, vectors src `sstride` elements apart
+// The right-hand-side block of a resumed factorisation (g3_gp_append): rows x npad at dst, row 0 = [a[0:n0), delta[n0:n), 0 ...]
+// -- what the sweep would have left in the first n0 columns, and the new entries it has yet to solve -- other rows 0.
+template <typename T>
+__global__ void append_rhs_kernel(T* dst, int64_t ld, const T* __restrict__ a, const T* __restrict__ delta, int64_t n0, int64_t n,
+                                  int64_t npad, int64_t rows) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= npad) return;
+  const T top = j < n0 ? a[j] : (j < n ? delta[j] : T(0));
+  for (int64_t r = 0; r < rows; ++r) dst[r * ld + j] = r == 0 ? top : T(0);
+}
+int g3i_append_rhs(g3_ctx* ctx, void* dst, int64_t ld, const void* a, const void* delta, int64_t n0, int64_t n, int64_t npad,
+                   int64_t rows, g3_dtype dt) {
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((append_rhs_kernel<T>), dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, ctx->stream, (T*)dst, ld,
+                       (const T*)a, (const T*)delta, n0, n, npad, rows);
+  });
+  G3_LAUNCH_CHECK();
+  return G3_OK;
+}
+
 static int pad_row_launch(g3_ctx* ctx, void* dst, int64_t ld, const void* src, int64_t n, int64_t npad, int64_t rows, g3_dtype dt,
                           int batch = 1, int64_t dstride = 0, int64_t sstride = 0) {
   g3_by_dtype(dt, [&](auto t) {
@@ -721,6 +743,36 @@ static int pad_row_launch(g3_ctx* ctx, void* dst, int64_t ld, const void* src, i
   });
   G3_LAUNCH_CHECK();
   return G3_OK;
+}
+
+// The tail of an evaluation (logp_finish_kernel): queued by the launch, its five doubles -- the four scalars and the pivot
+// flag -- brought to the host by the fetch, which synchronises.
+static int logp_finish_launch(g3_ctx* ctx, const void* K, int64_t N, int64_t Np, int64_t ldk, const void* rhs, void* a, int64_t a_from,
+                              g3_dtype dt) {
+  g3_by_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((logp_finish_kernel<T>), dim3(1), dim3(1024), 0, ctx->stream, (const T*)K, N, Np, ldk, (const T*)rhs, (T*)a,
+                       a_from, ctx->d_stats, ctx->d_info);
+  });
+  G3_LAUNCH_CHECK();
+  return G3_OK;
+}
+static int logp_finish_fetch(g3_ctx* ctx, double st5[5]) {
+  const int r = fetch_stats(ctx, st5, 5);
+  if (!r) { ctx->info_clean = true; ctx->info_sync = true; }      // the kernel left the pivot flag cleared, and the host has waited for it
+  return r;
+}
+int g3i_logp_finish(g3_ctx* ctx, const void* K, int64_t N, int64_t Np, int64_t ldk, const void* rhs, void* a, int64_t a_from, g3_dtype dt,
+                    double st5[5]) {
+  const int pr = g3i_prof_begin(ctx, G3_TAG_REDUCE, 0.0);
+  const int r = logp_finish_launch(ctx, K, N, Np, ldk, rhs, a, a_from, dt);
+  g3i_prof_end(ctx, pr);
+  return r ? r : logp_finish_fetch(ctx, st5);
+}
+// min, mean and max of a device vector on the host (synchronises): the diagonal statistics at a leading dimension of 0
+int g3i_vec_stats(g3_ctx* ctx, const void* v, int64_t n, g3_dtype dt, double out[3]) {
+  const int rc = diag_stats_launch(ctx, const_cast<void*>(v), n, 0, dt, ctx->d_stats + 8, 0);
+  return rc ? rc : fetch_stats(ctx, out, 3, 8);
 }
 
 // Shared implementation of g3_gp_factor / g3_gp_factor_predict.  K_dev is a tall buffer:
@@ -774,19 +826,12 @@ static int gp_factor_impl(g3_ctx* ctx, const g3_kernel_prog* prog, const void* X
   double st4[5];
   auto finish = [&]() -> int {
     const int pr = g3i_prof_begin(ctx, G3_TAG_REDUCE, 2.0 * N * M);
-    g3_by_dtype(dt, [&](auto t) {
-      using T = decltype(t);
-      hipLaunchKernelGGL((logp_finish_kernel<T>), dim3(1), dim3(1024), 0, ctx->stream, (const T*)K, N, Np, ldk, (const T*)rhs, (T*)a,
-                         ctx->d_stats, ctx->d_info);
-    });
-    G3_LAUNCH_CHECK();
-    int r = G3_OK;
+    int r = logp_finish_launch(ctx, K, N, Np, ldk, rhs, a, 0, dt);
+    if (r) return r;
     if (M > 0 && (mu || ss)) r = rows_dot_ss_launch(ctx, Vp, M, N, ldk, a, dt, mu, ss);
     g3i_prof_end(ctx, pr);
     if (r) return r;
-    r = fetch_stats(ctx, st4, 5);        // the one host synchronisation of a successful evaluation
-    if (!r) { ctx->info_clean = true; ctx->info_sync = true; }      // the kernel above left the pivot flag cleared, and the host has waited for it
-    return r;
+    return logp_finish_fetch(ctx, st4);  // the one host synchronisation of a successful evaluation
   };
   rc = build();
   if (rc) return rc;

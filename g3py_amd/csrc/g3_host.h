@@ -802,3 +802,45 @@ static inline void g3h_fold_groups(const int64_t* ptr, int nfold, size_t cap, Pe
 }
 // a *_batched_fields entry point's status from its whole-programs body's: lo .. -4 name arguments three places further there
 static inline int g3h_fields_status(int rc, int lo) { return (rc <= -4 && rc >= lo) ? rc - 3 : rc; }
+
+// ---- appending observations to a factor (g3_append.hip).  A lower Cholesky factor is built from its leading principal
+// submatrices: with N0 rows factored and N1 > N0 wanted, the whole 128-row blocks below n0 = rounddown(N0, 128) stay as they
+// are and the sweep resumes at block row n0, over r = Np1 - n0 rows up to Np1 = roundup(N1, 128) (the old last block, if it
+// was ragged, is recomputed: that takes its identity padding out without a special case).
+struct G3hAppendPlan {
+  int64_t n0, Np1, r;
+  int64_t k_rows;         // rows the tall buffer needs: Np1 plus the right-hand-side block
+  int64_t w_blocks;       // 128 x 128 block inverses in all; the call writes those from w_first on
+  int64_t w_first;
+  int64_t corner_off;     // element offset of the corner K[n0, n0] in a buffer of leading dimension ld
+  int64_t rows_off;       // ... of the first recomputed row K[n0, 0]
+  int64_t rhs_off;        // ... of the right-hand-side block K[Np1, 0]
+  int64_t w_off;          // ... of block inverse w_first in the compact inverse buffer
+};
+static inline G3hAppendPlan g3h_append_plan(int64_t N0, int64_t N1, int64_t ld) {
+  G3hAppendPlan p;
+  p.n0 = N0 / G3H_LB * G3H_LB;
+  p.Np1 = g3h_roundup(N1, G3H_LB);
+  p.r = p.Np1 - p.n0;
+  p.k_rows = p.Np1 + G3H_LB;
+  p.w_blocks = p.Np1 / G3H_LB;
+  p.w_first = p.n0 / G3H_LB;
+  p.rows_off = p.n0 * ld;
+  p.corner_off = p.rows_off + p.n0;
+  p.rhs_off = p.Np1 * ld;
+  p.w_off = p.w_first * G3H_LB * G3H_LB;
+  return p;
+}
+// N0, N1 of an append, at `at` and at + 1: at least one row factored, at least one row more wanted
+static inline int g3h_args_append(int64_t N0, int64_t N1, int at) {
+  if (N0 <= 0) return -at;
+  if (N1 <= N0) return -(at + 1);
+  return 0;
+}
+// Capacity (rows = leading dimension, a multiple of 128) of a buffer that must hold `need` rows and holds `have`: unchanged
+// while it fits, else at least 1.5 x what it was, so that a run of one-row appends reallocates O(log) times.
+static inline int64_t g3h_append_capacity(int64_t have, int64_t need) {
+  if (need <= have) return have;
+  const int64_t grown = g3h_roundup(have + (have + 1) / 2, G3H_LB), want = g3h_roundup(need, G3H_LB);
+  return grown > want ? grown : want;
+}

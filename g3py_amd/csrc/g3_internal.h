@@ -284,6 +284,16 @@ int g3i_rows_dot_ss_batched(g3_ctx* ctx, const void* V, int64_t m, int64_t n, in
 // rows_dot_ss over the upper triangle of a square Y (npad x npad): rows [0, n) from their diagonal on, rows [n, npad) get 0
 int g3i_rows_dot_ss_tri(g3_ctx* ctx, const void* Y, int64_t n, int64_t npad, int64_t ld, const void* a, g3_dtype dt, void* dot,
                         void* ss);
+// ---- pieces of g3_gp_factor that g3_gp_append (g3_append.hip) shares (g3_api.hip)
+// the right-hand-side block of a resumed factorisation: row 0 = [a[0:n0), delta[n0:n), 0 ...] over npad columns, rows 1 .. rows-1 zero
+int g3i_append_rhs(g3_ctx* ctx, void* dst, int64_t ld, const void* a, const void* delta, int64_t n0, int64_t n, int64_t npad,
+                   int64_t rows, g3_dtype dt);
+// the finishing reduction of an evaluation: a[a_from:Np) <- the solved row `rhs`, st5 = [sum log L_ii, a^T a, #non-finite a, #bad
+// diagonal entries] over the first N rows and the pivot flag, which is left cleared.  Synchronises the context's stream
+int g3i_logp_finish(g3_ctx* ctx, const void* K, int64_t N, int64_t Np, int64_t ldk, const void* rhs, void* a, int64_t a_from, g3_dtype dt,
+                    double st5[5]);
+// [min, mean, max] of a device vector of n entries, on the host (synchronises the context's stream)
+int g3i_vec_stats(g3_ctx* ctx, const void* v, int64_t n, g3_dtype dt, double out[3]);
 int g3i_ensure_invd(g3_ctx* ctx, int64_t n, g3_dtype dt);
 int g3i_ensure_work(g3_ctx* ctx, size_t bytes);
 int g3i_upload_prog(g3_ctx* ctx, const g3_kernel_prog* prog, int slot, const g3_kernel_prog** dptr);

@@ -362,6 +362,35 @@ class Device:
                                   mu.ptr if mu is not None else None, ss.ptr if ss is not None else None)
         _check(self, rc, 'g3_gp_cross')
 
+    # ---- appending observations to a factor (include/g3hip_online.h)
+    def copy2d(self, dst, src, rows, cols):
+        """dst[:rows, :cols] <- src[:rows, :cols] on the device (stream-ordered)"""
+        rc = self.lib.g3_copy2d(self.ctx, dst.ptr, dst.ld, src.ptr, src.ld, int(rows), int(cols), _lib.dtype_code(dst.dtype))
+        _check(self, rc, 'g3_copy2d')
+
+    def gp_append(self, prog, X, N0, N1, d, delta, K, W, a):
+        """after gp_factor (or gp_append) on the first N0 rows of X, with tries = 0, no fallback and info = 0: the factor, its
+        block inverses and a for the first N1 rows.  K needs roundup(N1) + 128 rows of ld >= roundup(N1), W roundup(N1) / 128
+        blocks, a and delta N1 entries (delta is read from rounddown(N0, 128) on).  Returns gp_factor's dict plus `refused`:
+        True when the diagonal of the N1 points would have been lifted (nothing was written); with `refused` or a non-zero
+        `info` the caller refits."""
+        if K.rows < roundup(N1) + _lib.G3_RHS_PAD:
+            raise G3Error('g3_gp_append needs a K buffer with roundup(N1) + 128 rows')
+        out = (C.c_double * 8)()
+        rc = self.lib.g3_gp_append(self.ctx, C.byref(prog), X.ptr, N0, N1, X.ld, d, delta.ptr, _lib.dtype_code(K.dtype),
+                                   K.ptr, K.ld, W.ptr, a.ptr, out)
+        _check(self, rc, 'g3_gp_append')
+        return dict(logdet=out[0], quad=out[1], nonfinite=out[2], tries=int(out[3]), fallback=bool(out[4]), info=int(out[5]),
+                    refused=bool(out[6]))
+
+    def gp_cross_append(self, prog, Xs, M, X, N0, N1, d, L, W, a, V, mu, ss):
+        """after gp_append from N0 to N1 rows: extend the cross solve gp_cross left in V (ld >= roundup(N1)) for the same Xs
+        and program by the new columns, and recompute mu and ss over all of them; stream-ordered"""
+        rc = self.lib.g3_gp_cross_append(self.ctx, C.byref(prog), Xs.ptr, M, Xs.ld, X.ptr, N0, N1, X.ld, d, L.ptr, L.ld,
+                                         W.ptr, a.ptr if a is not None else None, _lib.dtype_code(L.dtype), V.ptr, V.ld,
+                                         mu.ptr if mu is not None else None, ss.ptr if ss is not None else None)
+        _check(self, rc, 'g3_gp_cross_append')
+
     @staticmethod
     def _ptr(a):
         return a.ptr if a is not None else None

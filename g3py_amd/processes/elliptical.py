@@ -36,6 +36,7 @@ class EllipticalProcess(StochasticProcess):
         self._cache = None
         self._workspace = None
         self._dist = None
+        self.append_stats = dict(appended=0, cross_appended=0, refit=0)    # which way each observe_more went
         kwargs['space'] = space
         super().__init__(*args, **kwargs)
 
@@ -219,6 +220,142 @@ class EllipticalProcess(StochasticProcess):
         c['dx'] = None              # and predict_dx's L^-T and alpha
         c['cv'] = None              # and the leave-fold-out ones
         return st
+
+    # ---------------------------------------------------------------- new observations without a refit
+    _NP_SCRATCH = ('Y', 'Kinv', 'alpha', 'loo', 'cv', 'dloo', 'dxY', 'dxvec')    # workspace buffers sized by the padded N
+
+    def observe_more(self, inputs, outputs, params=None):
+        """Append observations: afterwards the process is what observed(all inputs, all outputs) would have made it, up to
+        rounding (the reference has no counterpart: it refits).  When the factor cached for these hyper-parameter values
+        (params=None: the current ones) and the observations so far was solved without jitter, fallback or pivot failure, on
+        one GPU, it is extended in place -- a lower Cholesky factor is built from its leading principal submatrices, so only
+        the block rows from rounddown(N, 128) on are computed (g3_gp_append), and a cached cross solve at the last space is
+        extended by the new columns (g3_gp_cross_append).  A following logp / predict / dlogp / loo on the same parameters
+        finds the factor.  Everywhere else -- no such factor, a jittered one, a diagonal the reference's tt_to_cov would
+        have lifted, a failed pivot among the new rows, several GPUs -- the data are extended, the cache is dropped and
+        the next call factors everything through the usual path.  `append_stats` counts which way each call went.  From the
+        first call on, the workspace carries slack and grows geometrically."""
+        Xn = self._x(inputs)
+        yn = np.asarray(outputs, dtype=self.dtype).reshape(-1)
+        if len(Xn) != len(yn):
+            raise _lib.G3Error('observe_more: %d inputs for %d outputs' % (len(Xn), len(yn)))
+        if len(Xn) == 0:
+            return
+        if not self.is_observed:
+            self.observed(Xn, yn)
+            self._cache = None
+            self.append_stats['refit'] += 1
+            return
+        X0, y0 = self._x(self._inputs), np.asarray(self._outputs, dtype=self.dtype).reshape(-1)
+        if Xn.shape[1] != X0.shape[1]:
+            raise _lib.G3Error('observe_more: inputs with %d columns, the process has %d' % (Xn.shape[1], X0.shape[1]))
+        X1, y1 = np.concatenate([X0, Xn]), np.concatenate([y0, yn])
+        values, _ = self._values(self.params if params is None else self.filter_params(params))
+        c = self._cache
+        key = tuple((k, np.asarray(v).tobytes()) for k, v in sorted(values.items()))
+        st = c['stats'] if c is not None else None
+        fast = (self._dist is None and st is not None and c['which'] is not None and c['key'] == (key, X0.shape)
+                and st['tries'] == 0 and not st['fallback'] and st['info'] == 0
+                and np.array_equal(c['X'], X0) and np.array_equal(c['y'], y0))
+        self.observed(X1, y1)
+        if fast:
+            try:
+                fast = self._append(c, values, key, Xn, yn, X1, y1)
+            except Exception:
+                self._cache = self._workspace = None
+                raise
+        if not fast:
+            self._cache = None
+            self.append_stats['refit'] += 1
+
+    def _reserve(self, c, N1):
+        """the factor workspace with room for N1 observations: capacity grows by >= 1.5 (a multiple of 128, the leading
+        dimension), what the factor of the whole blocks below n0 consists of is moved on the device; c's and the
+        workspace's buffers become views of N1 rows"""
+        dev, ws, t = self.device, self._workspace, self.dtype
+        back = ws.setdefault('back', {k: ws[k] for k in ('Kd', 'Wd', 'ad', 'Xd', 'dvec')})
+        N0, d, P = c['N'], c['d'], _lib.G3_PAD
+        n0, Np1 = N0 // P * P, _lib.roundup(N1)
+        old = []
+        cap = back['Kd'].ld
+        if Np1 > cap or back['Wd'].rows < Np1 or back['ad'].ld < Np1:
+            cap = _lib.append_capacity(cap, Np1)
+            new = dict(Kd=dev.alloc(cap + _lib.G3_RHS_PAD, cap, t), Wd=dev.alloc_inverses(cap, t), ad=dev.alloc(1, cap, t))
+            if n0 > 0:
+                dev.copy2d(new['Kd'], back['Kd'], n0, n0)
+                dev.copy2d(new['Wd'], back['Wd'], n0, P)
+                dev.copy2d(new['ad'], back['ad'], 1, n0)
+            old += [back[k] for k in new]
+            back.update(new)
+        if back['Xd'].rows < N1:
+            capx = _lib.append_capacity(back['Xd'].rows, N1)
+            Xd = dev.alloc(capx, d, t)
+            dev.copy2d(Xd, back['Xd'], N0, d)
+            old += [back['Xd'], back['dvec']]
+            back['Xd'], back['dvec'] = Xd, dev.alloc(1, capx, t)
+        views = dict(Kd=dev.wrap(back['Kd'].ptr, Np1 + _lib.G3_RHS_PAD, Np1, back['Kd'].ld, t, keep=back['Kd']),
+                     Wd=dev.wrap(back['Wd'].ptr, Np1, P, P, t, keep=back['Wd']),
+                     ad=dev.wrap(back['ad'].ptr, 1, Np1, back['ad'].ld, t, keep=back['ad']),
+                     Xd=dev.wrap(back['Xd'].ptr, N1, d, back['Xd'].ld, t, keep=back['Xd']),
+                     dvec=dev.wrap(back['dvec'].ptr, 1, N1, back['dvec'].ld, t, keep=back['dvec']))
+        ws.update(views)
+        return views, old
+
+    def _append(self, c, values, key, Xn, yn, X1, y1):
+        """the fast path of observe_more on the cached factor c; False: declined, the caller refits"""
+        dev, ws, t = self.device, self._workspace, self.dtype
+        N0, d, Np0 = c['N'], c['d'], c['Np']
+        N1, Np1 = len(X1), _lib.roundup(len(X1))
+        n0 = N0 // _lib.G3_PAD * _lib.G3_PAD
+        # the right-hand side of the new points alone: mapping and location are pointwise (elliptical.py:63)
+        mapped, mu, delta, det_m = self._delta(values, Xn, yn)
+        mapped_num = to_num(mapped, t)
+        delta1 = np.concatenate([c['delta'], delta])
+        post1 = np.concatenate([c['delta_post'], mapped_num - mu])
+        dl = delta1 if c['which'] == 'logp' else post1
+        v, old = self._reserve(c, N1)
+        dev.copy_in(dev.wrap(v['Xd'].offset(N0), N1 - N0, d, v['Xd'].ld, t, keep=v['Xd']), Xn)
+        dev.copy_in(v['dvec'], np.where(np.isfinite(dl), dl, 0).astype(t))
+        prog = self._prog(self.f_kernel_noise, values, d)
+        st = dev.gp_append(prog, v['Xd'], N0, N1, d, v['dvec'], v['Kd'], v['Wd'], v['ad'])
+        for b in old:
+            b.free()
+        if st.pop('refused') or st['info'] != 0:
+            self._workspace = None
+            return False
+        st['delta_finite'] = bool(np.all(np.isfinite(dl)))
+        if Np1 != Np0:
+            for k in self._NP_SCRATCH:
+                if k in ws:
+                    ws.pop(k).free()
+        ws['shape'], ws['X'] = X1.shape, X1.copy()
+        cross = c.get('cross')
+        c.update(key=(key, X1.shape), X=ws['X'].copy(), y=y1.copy(), N=N1, Np=Np1, delta=delta1, delta_post=post1,
+                 z=np.concatenate([c['z'], mapped_num]), mu=np.concatenate([c['mu'], mu]),
+                 det_m=np.asarray(c['det_m'] + det_m, dtype=t)[()], stats=st, grad=None, loo=None, cv=None, dx=None, cross=None,
+                 same_delta=bool(np.array_equal(delta1, post1)), **{k: v[k] for k in ('Xd', 'Kd', 'Wd', 'ad')})
+        self.append_stats['appended'] += 1
+        if cross is not None and cross['out'][0] is not None:
+            # the cross solve at the last space: its columns below n0 stand, the new ones are solved against the corner
+            V, _, _, M, Mp = cross['out']
+            if V.ld < Np1:
+                V2 = dev.alloc(Mp, _lib.append_capacity(V.ld, Np1), t)
+                if n0 > 0:
+                    dev.copy2d(V2, V, Mp, n0)
+                V, dead = V2, V
+            else:
+                dead = None
+            noise, _ = cross['kid']
+            kern = cross['kernel_ref'] if cross.get('kernel_ref') is not None else (self.f_kernel_noise if noise else self.f_kernel)
+            mud, ssd = dev.alloc(1, Mp, t), dev.alloc(1, Mp, t)
+            dev.gp_cross_append(self._prog(kern, values, d), dev.upload(cross['S']), M, c['Xd'], N0, N1, d, c['Kd'], c['Wd'], c['ad'],
+                                V, mud, ssd)
+            cross['out'] = (V, dev.download(mud, 1, M)[0], dev.download(ssd, 1, M)[0], M, Mp)
+            if dead is not None:
+                dead.free()
+            c['cross'] = cross
+            self.append_stats['cross_appended'] += 1
+        return True
 
     def _cross(self, c, values, space, noise, kernel=None):
         """V = K(space, X) L^-T, mu = V a, ss = |V_i|^2 (elliptical.py:78-91)"""
